@@ -1,6 +1,6 @@
 """bench.py -- headline benchmark (BASELINE.json metric).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 Metric: Msamples/s of the batched STFT -> iSTFT -> OLA round trip at
@@ -8,12 +8,21 @@ frame=1024 hop=256 batch=1024 (1024 synthetic mono streams x 480 000 samples
 of 48 kHz audio = 10 s each, per GPU), inputs and outputs resident in HBM.
 A "step" is one crlot_roundtrip over the whole batch.
 
+A plain run does what the headline needs and nothing else: set up, clock ramp,
+`--warmup` untimed steps, `--steps` timed steps, the result line (the roofline
+block is priced from the timed steps' own HIP events).  `--dump-outputs DIR`
+then writes what the last timed step left in the output buffer (rank 0; a
+fixed, seeded sample of it, see dump_outputs).  `--full` adds the legs that
+take runs of their own: the strong phase and the CPU baseline (`--no-strong`,
+`--no-cpu-baseline` drop one of them again); without it `strong_scaling` and
+`cpu_baseline` are null.  `--suite NAME` is a program of its own, as before.
+
 Multi-GPU: one process per GPU.  `--gpus N` without an external
 launcher starts the N ranks itself (dist.launch: fresh child processes, the
 parent never touches the GPU).  Streams are independent, so there is no
 data-path collective; the control plane (start/stop barrier, max-over-ranks
 time) runs over RCCL when every rank owns a GPU, over gloo when ranks share one.
-Two phases are timed:
+Two phases are timed, the second under `--full` only:
   weak    (the headline `value`)  every rank runs its own 1024 streams;
   strong  (BASELINE config 5)     8192 streams in total, rank r takes
                                   dist.stream_range(8192, N, r).
@@ -30,7 +39,7 @@ Besides the contract fields the JSON line carries
   cpu_baseline  the oracle's C restatement of the reference CPU path (kissfft
                 algorithm + scalar-FMA OLA, "kind": "port") timed on this host,
                 rank 0 at N=1 only, on a bounded sample of streams, at the
-                host's CPU share and single-threaded.
+                host's CPU share and single-threaded (`--full` only).
 """
 from __future__ import annotations
 
@@ -297,6 +306,44 @@ def synth_device(torch, S: int, T: int, dev, seed: int):
     x = torch.empty((S, T), dtype=torch.float32, device=dev)
     x.uniform_(-0.5, 0.5, generator=g)
     return x
+
+
+DUMP_SEED = 0xD0D0          # the sample below is the same for every run and build
+DUMP_ROWS = 16              # whole streams kept (16 x ~480 000 f32 = ~31 MB at the headline shape)
+DUMP_POINTS = 1 << 22       # single samples kept from the whole batch (16 MB)
+DUMP_WHOLE_BYTES = 16 << 20  # an output this small is written whole instead
+
+
+def dump_outputs(torch, y, out_dir: str) -> dict:
+    """Write what the timed round trip left in its output buffer `y` (streams x
+    produced samples, f32: what a caller of plan.roundtrip receives) under
+    out_dir as float32 .npy files, < 48 MB in all:
+      roundtrip.npy          the whole of y when it is at most 16 MiB, else
+      roundtrip_rows.npy     DUMP_ROWS whole streams (row indices drawn once from
+                             DUMP_SEED, ascending) and
+      roundtrip_points.npy   DUMP_POINTS samples of the flattened batch (flat
+                             indices drawn from the same generator, ascending).
+    The indices depend on y's shape and DUMP_SEED alone, and the inputs on the
+    seed in synth_device, so two builds run with the same arguments write
+    arrays that compare element for element."""
+    os.makedirs(out_dir, exist_ok=True)
+    S, L = y.shape
+    files = {}
+
+    def save(name, t):
+        a = np.ascontiguousarray(t.detach().cpu().numpy(), dtype=np.float32)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        files[name + ".npy"] = list(a.shape)
+
+    if S * L * 4 <= DUMP_WHOLE_BYTES:
+        save("roundtrip", y)
+        return files
+    rng = np.random.default_rng(DUMP_SEED)
+    rows = np.sort(rng.choice(S, size=min(DUMP_ROWS, S), replace=False))
+    flat = np.sort(rng.integers(0, S * L, size=DUMP_POINTS, dtype=np.int64))
+    save("roundtrip_rows", y[torch.from_numpy(rows).to(y.device)])
+    save("roundtrip_points", y.reshape(-1)[torch.from_numpy(flat).to(y.device)])
+    return files
 
 
 
@@ -836,8 +883,14 @@ def main():
     ap.add_argument("--strong-steps", type=int, default=10)
     ap.add_argument("--no-strong", action="store_true")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--suite", choices=sorted(SUITES), help="run one reference bench/ counterpart instead")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the strong phase (config 5) and the CPU baseline; a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's output (rank 0, a fixed seeded sample) as DIR/*.npy")
+    ap.add_argument("--suite",choices=sorted(SUITES), help="run one reference bench/ counterpart instead")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.suite:
         return run_suite(args.suite)
 
@@ -869,6 +922,7 @@ def main():
     y = torch.empty((S, L), dtype=torch.float32, device=dev)
     ramp, mine = {}, {}
     elapsed_max, kern_ms = timed_phase(plan, x, y, args.steps, args.warmup, D, dev, torch, ramp, mine)
+    dumped = dump_outputs(torch, y, args.dump_outputs) if args.dump_outputs and rank == 0 else None
     del x, y
     # every rank's device, kernel time and own wall time: who set the max (a first
     # 8-GPU run names its straggler)
@@ -884,7 +938,7 @@ def main():
 
     # ---- strong phase (config 5): a fixed 8192-stream job sharded over the ranks
     strong = None
-    if not args.no_strong and args.strong_streams > 0:
+    if args.full and not args.no_strong and args.strong_streams > 0:
         lo, hi = D.stream_range(args.strong_streams, world, rank)
         xs = synth_device(torch, hi - lo, T, dev, 0x5EED0000 + lo)
         ys = torch.empty((hi - lo, L), dtype=torch.float32, device=dev)
@@ -903,7 +957,7 @@ def main():
         }
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             cpu = cpu_baseline()
         except Exception as e:  # reported, never fatal to the GPU number
@@ -967,8 +1021,11 @@ def main():
                         "size the group reports and the distinct devices (PCI ids) its ranks ran on",
             },
             "cpu_baseline": cpu,
+            "full": args.full,
             "build": build,
         }
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "files": dumped}
         print(json.dumps(out), flush=True)
     D.finalize()
 

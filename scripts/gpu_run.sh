@@ -8,7 +8,7 @@
 #   smoke             __graft_entry__.smoke()
 #   ab[:N/H]          scripts/ab_bench.py at N/H (default 1024/256) over abtmp/*.so
 #   abgain:N/H        the same with a spectral gain
-#   bench             bench.py (driver flags: --steps 20 --warmup 5)
+#   bench             bench.py --steps 20 --warmup 5 --full
 #   configs           scripts/bench_configs.py
 #   suite:NAME        bench.py --suite NAME
 #   profile           scripts/profile_round.sh TAG + make_profile_summary.py TAG
@@ -44,7 +44,7 @@ for s in "$@"; do
     abgain)
       n=${arg%%/*}; h=${arg#*/}
       AB_GAIN=1 AB_N=$n AB_H=$h AB_GLOB="abtmp/*.so" AB_ROUNDS=${AB_ROUNDS:-8} run "abgain_${n}_${h}" 400 python -u scripts/ab_bench.py ;;
-    bench) run bench 600 python bench.py --steps 20 --warmup 5 ;;
+    bench) run bench 600 python bench.py --steps 20 --warmup 5 --full ;;
     configs) run configs 600 python scripts/bench_configs.py ;;
     suite) run "suite_$arg" 600 python bench.py --suite "$arg" ;;
     profile)

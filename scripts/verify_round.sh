@@ -16,5 +16,5 @@ step() {  # step NAME SECONDS CMD...
 }
 step pytest_gpu 900 python -u -m pytest tests -m gpu -x -q -p no:cacheprovider --timeout 300 --timeout-method thread
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
-step bench 600 python bench.py
+step bench 600 python bench.py --full
 echo "== done $(date +%T)"

@@ -67,7 +67,7 @@ def test_two_ranks_one_gpu_hip_bit_exact(tmp_path, torch_cuda, pkg, oracle):
 def test_bench_launches_its_own_ranks(torch_cuda):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2",
            "--warmup", "1", "--streams", "8", "--strong-streams", "16", "--strong-steps", "2",
-           "--no-cpu-baseline"]
+           "--no-cpu-baseline", "--full"]  # (--full: the strong phase asserted below)
     env = {k: v for k, v in os.environ.items()
            if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE")}
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env)

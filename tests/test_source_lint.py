@@ -41,7 +41,7 @@ typedef float pc __attribute__((ext_vector_type(2)));
 
 
 @pytest.mark.parametrize("snippet,bad", [
-    (PRE_8B3B77B, True),
+    pytest.param(PRE_8B3B77B, True, id="pre_8b3b77b_pair1k-True"),  # (a short id: the snippet spans lines)
     ("float2 v; unsigned a = __builtin_bit_cast(unsigned, v.x);", True),
     ("auto v = __builtin_amdgcn_raw_buffer_load_b64(r, 0, 0, 0); float f = __builtin_bit_cast(float, v[1]);", True),
     ("pc v[16]; float f = __builtin_bit_cast(float, v[3][1]);", True),

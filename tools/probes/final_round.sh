@@ -22,6 +22,6 @@ step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
 rm -rf $OUT/prof_$TAG
 step profile 900 bash scripts/profile_round.sh $TAG
 step summary 120 python scripts/make_profile_summary.py $TAG
-step bench 600 python bench.py
+step bench 600 python bench.py --full
 step configs 600 python scripts/bench_configs.py
 echo "== done $(date +%T)"
