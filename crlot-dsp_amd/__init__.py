@@ -149,6 +149,9 @@ def lib():
         "crlot_stream_destroy": ([vp], None),
         "crlot_stream_reset": ([vp], C.c_int),
         "crlot_stream_push_hop": ([vp, vp, vp, C.POINTER(i32), vp], C.c_int),
+        "crlot_stream_stft_hop": ([vp, vp, vp, i64, C.POINTER(i32), vp], C.c_int),
+        "crlot_stream_istft_hop": ([vp, vp, i64, vp, i64, vp, vp], C.c_int),
+        "crlot_stream_push_hop_masked": ([vp, vp, vp, i64, vp, C.POINTER(i32), vp], C.c_int),
         "crlot_stream_set_layout": ([vp, i32], C.c_int),
         "crlot_stream_rt_create": ([vp, i32, i32, i32, C.POINTER(vp)], C.c_int),
         "crlot_stream_rt_destroy": ([vp], None),
@@ -888,6 +891,100 @@ class Stream:
         s = _stream_handle(hop) if stream is None else stream
         _check(lib().crlot_stream_push_hop(self._h, hop.data_ptr(), out.data_ptr(), C.byref(em), s),
                "crlot_stream_push_hop")
+        return out, em.value
+
+    # -- the hop with a time-varying spectral step (crlot_stream_stft_hop / _istft_hop / _push_hop_masked)
+    def _hop_arg(self, hop, what="hop"):
+        torch = _torch()
+        H = self.plan.hop_size
+        shape = (H, self.channels) if self.interleaved else (self.channels, H)
+        if not torch.is_tensor(hop) or hop.dtype != torch.float32 or not hop.is_cuda:
+            raise ValueError(f"{what} must be a float32 device tensor")
+        if tuple(hop.shape) != shape or not hop.is_contiguous():
+            raise ValueError(f"{what} must be a contiguous {shape} tensor")
+        return hop
+
+    def _spec_arg(self, spec):
+        """(channels, N/2+1) complex64 device rows -> ld_spec in floats."""
+        torch = _torch()
+        bins = self.plan.frame_size // 2 + 1
+        if not torch.is_tensor(spec) or spec.dtype != torch.complex64 or not spec.is_cuda:
+            raise ValueError("spec must be a complex64 device tensor")
+        if tuple(spec.shape) != (self.channels, bins) or spec.stride(1) != 1:
+            raise ValueError(f"spec must be ({self.channels}, {bins}) with contiguous rows")
+        ld = _ld(spec, 0, bins)
+        if ld < bins:
+            raise ValueError("spec rows overlap")
+        return 2 * ld
+
+    def _mask_arg(self, mask, like):
+        """A mask of (channels, N/2+1) rows or one shared (N/2+1,) row -> (pointer, ld_mask);
+        checked here, because the C entry sees only a pointer."""
+        torch = _torch()
+        bins = self.plan.frame_size // 2 + 1
+        if mask is None:
+            return None, 0
+        if not torch.is_tensor(mask) or mask.dtype != torch.float32:
+            raise ValueError("mask must be a float32 tensor")
+        if not mask.is_cuda or mask.device != like.device:
+            raise ValueError("mask must be on the stream's device")
+        if tuple(mask.shape) == (bins,):
+            if mask.stride(0) != 1:
+                raise ValueError("mask row must be contiguous")
+            return mask.data_ptr(), 0
+        if tuple(mask.shape) != (self.channels, bins) or mask.stride(1) != 1:
+            raise ValueError(f"mask must be ({self.channels}, {bins}) or ({bins},) with contiguous rows")
+        ld = _ld(mask, 0, bins)
+        if ld < bins:
+            raise ValueError("mask rows overlap")
+        return mask.data_ptr(), ld
+
+    def stft_hop(self, hop, spec=None, stream: int | None = None) -> tuple:
+        """The analysis half of push_hop.  hop as push_hop's; returns (spec, emitted):
+        spec a (channels, N/2+1) complex64 tensor holding, when emitted is 1, the
+        spectrum of the frame this hop completes (Plan.stft's row), else untouched."""
+        torch = _torch()
+        hop = self._hop_arg(hop)
+        if spec is None:
+            spec = torch.empty((self.channels, self.plan.frame_size // 2 + 1), dtype=torch.complex64,
+                               device=hop.device)
+        ld = self._spec_arg(spec)
+        em = C.c_int32()
+        s = _stream_handle(hop) if stream is None else stream
+        _check(lib().crlot_stream_stft_hop(self._h, hop.data_ptr(), spec.data_ptr(), ld, C.byref(em), s),
+               "crlot_stream_stft_hop")
+        return spec, em.value
+
+    def istft_hop(self, spec, mask=None, out=None, stream: int | None = None):
+        """The synthesis half: spec (channels, N/2+1) complex64 -> the plan's gain, then
+        `mask` ((channels, N/2+1) or (N/2+1,) float32, optional) -> inverse, overlap-add
+        -> the next output block, laid out as a hop.  Returns the block."""
+        torch = _torch()
+        ld = self._spec_arg(spec)
+        mp, ldm = self._mask_arg(mask, spec)
+        H = self.plan.hop_size
+        if out is None:
+            out = torch.empty((H, self.channels) if self.interleaved else (self.channels, H), dtype=torch.float32,
+                              device=spec.device)
+        self._hop_arg(out, "out")
+        s = _stream_handle(spec) if stream is None else stream
+        _check(lib().crlot_stream_istft_hop(self._h, spec.data_ptr(), ld, mp, ldm, out.data_ptr(), s),
+               "crlot_stream_istft_hop")
+        return out
+
+    def push_hop_masked(self, hop, mask, out=None, stream: int | None = None) -> tuple:
+        """push_hop with a mask row ((channels, N/2+1) or (N/2+1,) float32; None: no
+        mask) for the frame this hop completes.  Returns (out, emitted), emitted 0 or H."""
+        torch = _torch()
+        hop = self._hop_arg(hop)
+        mp, ldm = self._mask_arg(mask, hop)
+        if out is None:
+            out = torch.empty_like(hop)
+        self._hop_arg(out, "out")
+        em = C.c_int32()
+        s = _stream_handle(hop) if stream is None else stream
+        _check(lib().crlot_stream_push_hop_masked(self._h, hop.data_ptr(), mp, ldm, out.data_ptr(), C.byref(em), s),
+               "crlot_stream_push_hop_masked")
         return out, em.value
 
 

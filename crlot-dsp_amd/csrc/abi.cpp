@@ -1691,7 +1691,10 @@ struct crlot_stream {
     int channels = 0;
     int interleaved = 0;
     bool any = false;  // any-shape kernel (fft_any.h) instead of k_stream_hop
-    int64_t q = 0;     // hops pushed so far
+    int64_t q = 0;     // hops pushed so far (split mode: hops analysed by stft_hop)
+    int64_t kf = 0;    // split mode: frames synthesised by istft_hop
+    int mode = 0;      // fixed by the first call after create / reset: 1 whole (push_hop,
+                       // push_hop_masked), 2 split (stft_hop, istft_hop); 0 not yet
     float* d_hist = nullptr;
     float* d_acc = nullptr;
     size_t hist_floats = 0, acc_floats = 0;
@@ -1757,6 +1760,40 @@ int crlot_stream_reset(crlot_stream* st) {
         (e = hipMemset(st->d_acc, 0, sizeof(float) * st->acc_floats)))
         return hip_fail(e, "hipMemset(stream state)");
     st->q = 0;
+    st->kf = 0;
+    st->mode = 0;
+    return CRLOT_OK;
+}
+
+// whole (1) and split (2) calls do not mix on one object between resets
+static int stream_enter(crlot_stream* st, int mode) {
+    if (st->mode && st->mode != mode)
+        return fail(CRLOT_ERUNTIME, mode == 1 ? "stream is in split mode (stft_hop / istft_hop); call "
+                                                "crlot_stream_reset before push_hop / push_hop_masked"
+                                              : "stream is in whole-hop mode (push_hop / push_hop_masked); call "
+                                                "crlot_stream_reset before stft_hop / istft_hop");
+    st->mode = mode;
+    return CRLOT_OK;
+}
+
+// the frame hop q completes under the DROP Framer, or -1
+static int64_t stream_frame_of_hop(const crlot_stream* st, int64_t q) {
+    const int64_t n = st->plan->geo.n, H = st->plan->geo.h;
+    const int64_t fc = drop_frames_after(q + 1, n, H), fp = drop_frames_after(q, n, H);
+    return fc > fp ? fc - 1 : -1;
+}
+
+static int check_spec_row(const crlot_stream* st, const void* d_spec, int64_t ld_spec) {
+    if (!d_spec) return fail(CRLOT_EINVAL, "null buffer");
+    if ((ld_spec & 1) || ld_spec < int64_t(st->plan->geo.n) + 2)
+        return fail(CRLOT_EINVAL, "ld_spec must be even and at least N + 2 floats");
+    if (reinterpret_cast<uintptr_t>(d_spec) & 7u) return fail(CRLOT_EINVAL, "d_spec must be 8-byte aligned");
+    return CRLOT_OK;
+}
+
+static int check_mask_row(const crlot_stream* st, const float* d_mask, int64_t ld_mask) {
+    if (d_mask && ld_mask != 0 && ld_mask < int64_t(st->plan->geo.n) / 2 + 1)
+        return fail(CRLOT_EINVAL, "ld_mask must be 0 (one shared row) or at least N/2 + 1 floats");
     return CRLOT_OK;
 }
 
@@ -1771,6 +1808,7 @@ int crlot_stream_push_hop(crlot_stream* st, const float* d_in, float* d_out, int
     if (emitted) *emitted = 0;
     if (!st) return fail(CRLOT_EINVAL, "null stream");
     if (!d_in || !d_out) return fail(CRLOT_EINVAL, "null buffer");
+    if (int rc = stream_enter(st, 1)) return rc;
     crlot_plan* p = st->plan;
     DeviceGuard g(p->device);
     const int64_t C = st->channels, H = p->geo.h;
@@ -1794,6 +1832,68 @@ int crlot_stream_push_hop(crlot_stream* st, const float* d_in, float* d_out, int
     const int64_t nb = p->geo.n / H;
     if (emitted) *emitted = (st->q >= nb - 1) ? int32_t(H) : 0;
     st->q += 1;
+    return CRLOT_OK;
+}
+
+int crlot_stream_push_hop_masked(crlot_stream* st, const float* d_in, const float* d_mask, int64_t ld_mask,
+                                 float* d_out, int32_t* emitted, void* stream) {
+    if (emitted) *emitted = 0;
+    if (!st) return fail(CRLOT_EINVAL, "null stream");
+    if (!d_in || !d_out) return fail(CRLOT_EINVAL, "null buffer");
+    if (int rc = check_mask_row(st, d_mask, ld_mask)) return rc;
+    if (!d_mask) return crlot_stream_push_hop(st, d_in, d_out, emitted, stream);  // no mask: the plain hop
+    if (int rc = stream_enter(st, 1)) return rc;
+    crlot_plan* p = st->plan;
+    DeviceGuard g(p->device);
+    const int64_t C = st->channels, H = p->geo.h;
+    const int64_t ld = st->interleaved ? 1 : H, inc = st->interleaved ? C : 1;
+    const int64_t k = stream_frame_of_hop(st, st->q);
+    hipError_t e = crlot::launch_stream_masked_hop(p->geo, tables(p), p->d_twany, st->any, d_in, ld, inc, d_mask,
+                                                   ld_mask, d_out, ld, inc, st->d_hist, st->d_acc, st->channels,
+                                                   st->q, k, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(e, "stream kernel launch");
+    if (emitted) *emitted = k >= 0 ? int32_t(H) : 0;
+    st->q += 1;
+    return CRLOT_OK;
+}
+
+int crlot_stream_stft_hop(crlot_stream* st, const float* d_in, float* d_spec, int64_t ld_spec, int32_t* emitted,
+                          void* stream) {
+    if (emitted) *emitted = 0;
+    if (!st) return fail(CRLOT_EINVAL, "null stream");
+    if (!d_in) return fail(CRLOT_EINVAL, "null buffer");
+    if (int rc = check_spec_row(st, d_spec, ld_spec)) return rc;
+    if (int rc = stream_enter(st, 2)) return rc;
+    crlot_plan* p = st->plan;
+    DeviceGuard g(p->device);
+    const int64_t C = st->channels, H = p->geo.h;
+    const int64_t ld = st->interleaved ? 1 : H, inc = st->interleaved ? C : 1;
+    const int64_t k = stream_frame_of_hop(st, st->q);
+    hipError_t e = crlot::launch_stream_stft_hop(p->geo, tables(p), p->d_twany, st->any, d_in, ld, inc, d_spec,
+                                                 ld_spec, st->d_hist, st->channels, st->q, k,
+                                                 static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(e, "stream kernel launch");
+    if (emitted) *emitted = k >= 0 ? 1 : 0;
+    st->q += 1;
+    return CRLOT_OK;
+}
+
+int crlot_stream_istft_hop(crlot_stream* st, const float* d_spec, int64_t ld_spec, const float* d_mask,
+                           int64_t ld_mask, float* d_out, void* stream) {
+    if (!st) return fail(CRLOT_EINVAL, "null stream");
+    if (!d_out) return fail(CRLOT_EINVAL, "null buffer");
+    if (int rc = check_spec_row(st, d_spec, ld_spec)) return rc;
+    if (int rc = check_mask_row(st, d_mask, ld_mask)) return rc;
+    if (int rc = stream_enter(st, 2)) return rc;
+    crlot_plan* p = st->plan;
+    DeviceGuard g(p->device);
+    const int64_t C = st->channels, H = p->geo.h;
+    const int64_t ld = st->interleaved ? 1 : H, inc = st->interleaved ? C : 1;
+    hipError_t e = crlot::launch_stream_istft_hop(p->geo, tables(p), p->d_twany, st->any, d_spec, ld_spec, d_mask,
+                                                  ld_mask, d_out, ld, inc, st->d_acc, st->channels, st->kf,
+                                                  static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(e, "stream kernel launch");
+    st->kf += 1;
     return CRLOT_OK;
 }
 

@@ -218,10 +218,13 @@ __device__ __forceinline__ cf rmerge(const cf& xk, const cf& xpk, const cf& w, i
 
 // kiss_fftr split -> gain -> kiss_fftri merge, src (Z) -> dst (Z'), with the
 // arithmetic of fft_wave.h real_split_hook_merge.  spec (optional) gets X[k],
-// k <= P.  st: exp(-i pi (k/P + 1/2)), k < P.
-template <bool HAS_GAIN>
+// k <= P.  st: exp(-i pi (k/P + 1/2)), k < P.  HAS_MASK: a real mask row (P + 1
+// floats) multiplies X after the gain, (X * gain) * mask on re and im each.
+// MERGE = false: the split alone (dst untouched; spec may be a row in global memory).
+template <bool HAS_GAIN, bool HAS_MASK = false, bool MERGE = true>
 __device__ __forceinline__ void split_merge(const cf* src, cf* dst, int p, const cf* st,
-                                            const float* gain, cf* spec, int lane) {
+                                            const float* gain, cf* spec, int lane,
+                                            const float* mask = nullptr) {
     for (int k = lane; k < p; k += 64) {
         const cf zk = src[k];
         const cf fpnk = conj(src[(p - k) % p]);
@@ -237,15 +240,22 @@ __device__ __forceinline__ void split_merge(const cf* src, cf* dst, int p, const
             xk = {xk.r * gk, xk.i * gk};
             xpk = {xpk.r * gpk, xpk.i * gpk};
         }
+        if constexpr (HAS_MASK) {
+            const float mk = mask[k], mpk = mask[p - k];
+            xk = {xk.r * mk, xk.i * mk};
+            xpk = {xpk.r * mpk, xpk.i * mpk};
+        }
         if (spec) {
             spec[k] = xk;
             if (k == 0) spec[p] = xpk;
         }
-        const cf fek = {xk.r + xpk.r, xk.i - xpk.i};
-        const cf tmp = {xk.r - xpk.r, xk.i + xpk.i};
-        dst[k] = k == 0 ? dc_merge(xk, xpk)
-                        : cf{__builtin_fmaf(tmp.r, w.r, __builtin_fmaf(tmp.i, w.i, fek.r)),
-                             __builtin_fmaf(tmp.i, w.r, __builtin_fmaf(-tmp.r, w.i, fek.i))};
+        if constexpr (MERGE) {
+            const cf fek = {xk.r + xpk.r, xk.i - xpk.i};
+            const cf tmp = {xk.r - xpk.r, xk.i + xpk.i};
+            dst[k] = k == 0 ? dc_merge(xk, xpk)
+                            : cf{__builtin_fmaf(tmp.r, w.r, __builtin_fmaf(tmp.i, w.i, fek.r)),
+                                 __builtin_fmaf(tmp.i, w.r, __builtin_fmaf(-tmp.r, w.i, fek.i))};
+        }
     }
 }
 

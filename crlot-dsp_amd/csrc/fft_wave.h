@@ -456,10 +456,15 @@ __device__ __forceinline__ cf dc_merge(cf x0, cf xp) { return {x0.r + xp.r, x0.r
 //   st : super twiddles exp(-i pi (k/P + 1/2)), k in [0, P)
 //   sth: 0.5 * st (exact), so X[k] = fma(f1, 1/2, f2 * sth) with no extra multiply
 // spec (optional): receives X[k] for k = lane + 64 m and X[P] from lane 0.
-template <int E, bool HAS_GAIN, bool WRITE_SPEC>
+// HAS_MASK: after the gain, a per-frame real mask -- mk[m] = mask[k], mpk[m] =
+// mask[P-k] in the lane's registers -- multiplies re and im of X[k] and X[P-k]
+// (the step is (X * gain) * mask).  MERGE = false stops after the split (v is
+// left as it came: a forward transform that only writes its spectrum).
+template <int E, bool HAS_GAIN, bool WRITE_SPEC, bool HAS_MASK = false, bool MERGE = true>
 __device__ __forceinline__ void real_split_hook_merge(cf (&v)[E], cf* buf, const cf* st,
                                                       const cf* sth, const float* gain,
-                                                      int lane, cf* spec = nullptr) {
+                                                      int lane, cf* spec = nullptr,
+                                                      const float* mk = nullptr, const float* mpk = nullptr) {
     constexpr int P = 64 * E;
 #pragma unroll
     for (int m = 0; m < E; ++m) buf[lane + 64 * m] = v[m];  // conflict free unswizzled
@@ -488,17 +493,23 @@ __device__ __forceinline__ void real_split_hook_merge(cf (&v)[E], cf* buf, const
             xk = {xk.r * gk, xk.i * gk};
             xpk = {xpk.r * gpk, xpk.i * gpk};
         }
+        if constexpr (HAS_MASK) {
+            xk = {xk.r * mk[m], xk.i * mk[m]};
+            xpk = {xpk.r * mpk[m], xpk.i * mpk[m]};
+        }
         if constexpr (WRITE_SPEC) {
             spec[k] = xk;
             if (k == 0) spec[P] = xpk;
         }
-        // kiss_fftri merge: Z'[k] = (X[k] + conj X[P-k]) + (X[k] - conj X[P-k]) conj(st)
-        const cf w = st[k];
-        const cf fek = {xk.r + xpk.r, xk.i - xpk.i};
-        const cf tmp = {xk.r - xpk.r, xk.i + xpk.i};
-        v[m].r = __builtin_fmaf(tmp.r, w.r, __builtin_fmaf(tmp.i, w.i, fek.r));
-        v[m].i = __builtin_fmaf(tmp.i, w.r, __builtin_fmaf(-tmp.r, w.i, fek.i));
-        if (m == 0 && lane == 0) v[0] = dc_merge(xk, xpk);
+        if constexpr (MERGE) {
+            // kiss_fftri merge: Z'[k] = (X[k] + conj X[P-k]) + (X[k] - conj X[P-k]) conj(st)
+            const cf w = st[k];
+            const cf fek = {xk.r + xpk.r, xk.i - xpk.i};
+            const cf tmp = {xk.r - xpk.r, xk.i + xpk.i};
+            v[m].r = __builtin_fmaf(tmp.r, w.r, __builtin_fmaf(tmp.i, w.i, fek.r));
+            v[m].i = __builtin_fmaf(tmp.i, w.r, __builtin_fmaf(-tmp.r, w.i, fek.i));
+            if (m == 0 && lane == 0) v[0] = dc_merge(xk, xpk);
+        }
     }
 }
 

@@ -208,6 +208,29 @@ hipError_t launch_stream_hop(const Geometry& g, const DevTables& t, const float*
                              int64_t in_inc, float* out, int64_t out_ld, int64_t out_inc,
                              float* hist, float* acc, int channels, int64_t q, hipStream_t stream);
 
+// The per-hop path cut at its spectral step (stream_spec.hip), on the same
+// per-object state: `any` picks the any-shape kernels (hist / acc sized as
+// launch_stream_any's, twany set), else the register-resident ones (fused shapes).
+// Spectra: channel c's N/2+1 float pairs at spec + c ld_spec (8-byte aligned rows);
+// mask: channel c's N/2+1 floats at mask + c ld_mask (0: one shared row).
+//   stft_hop    hop q into hist; when it completes DROP frame k >= 0 (k < 0: none)
+//               the frame's spectrum, before the gain, into spec.  acc untouched.
+//   istft_hop   frame k from spec: (X gain) mask (mask nullable), inverse, OLA,
+//               block k into out.  hist untouched.
+//   masked_hop  launch_stream_hop / launch_stream_any with the mask row (not null)
+//               of the frame the hop completes between split and merge.
+hipError_t launch_stream_stft_hop(const Geometry& g, const DevTables& t, const float* twany, bool any,
+                                  const float* in, int64_t in_ld, int64_t in_inc, float* spec, int64_t ld_spec,
+                                  float* hist, int channels, int64_t q, int64_t k, hipStream_t stream);
+hipError_t launch_stream_istft_hop(const Geometry& g, const DevTables& t, const float* twany, bool any,
+                                   const float* spec, int64_t ld_spec, const float* mask, int64_t ld_mask, float* out,
+                                   int64_t out_ld, int64_t out_inc, float* acc, int channels, int64_t k,
+                                   hipStream_t stream);
+hipError_t launch_stream_masked_hop(const Geometry& g, const DevTables& t, const float* twany, bool any,
+                                    const float* in, int64_t in_ld, int64_t in_inc, const float* mask,
+                                    int64_t ld_mask, float* out, int64_t out_ld, int64_t out_inc, float* hist,
+                                    float* acc, int channels, int64_t q, int64_t k, hipStream_t stream);
+
 // Resident streaming kernel (stream_rt.hip, BASELINE config 4).  The control
 // block and the hop rings live in pinned host memory; the host writes hop q
 // into in_ring slot q % depth, then seq = q + 1; workgroup w publishes

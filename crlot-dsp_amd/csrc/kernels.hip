@@ -33,6 +33,7 @@
 #include "fft_wave.h"
 #include "fused_common.h"
 #include "kernels.h"
+#include "stream_common.h"
 
 namespace crlot {
 
@@ -42,45 +43,8 @@ namespace {
 
 using namespace fk;
 
-constexpr int kWaves = 4;  // waves per 256-thread workgroup, each independent
-constexpr int kBlock = 64 * kWaves;
-
-template <int P>
-__host__ __device__ constexpr int xbuf_elems() {
-    return P;
-}
-
-// LDS carve shared by the kernels: [tw P cf][st P cf][sth P cf][wa N f][ws N f][bufs]
-template <int E>
-struct Lds {
-    static constexpr int P = 64 * E;
-    static constexpr int N = 2 * P;
-    static constexpr size_t bytes =
-        sizeof(cf) * (3 * P) + sizeof(float) * (2 * N) + sizeof(cf) * kWaves * xbuf_elems<P>();
-};
-
-template <int E>
-__device__ __forceinline__ void load_tables(const DevTables& t, cf* tw, cf* st, cf* sth, float* wa,
-                                            float* ws, bool need_windows, const float* ws_src = nullptr) {
-    constexpr int P = 64 * E, N = 2 * P;
-    const cf* gtw = reinterpret_cast<const cf*>(t.tw);
-    const cf* gst = reinterpret_cast<const cf*>(t.st);
-    for (int i = threadIdx.x; i < dev::twiddle_table_size(E); i += kBlock) tw[i] = gtw[i];
-    for (int i = threadIdx.x; i < P; i += kBlock) {
-        const cf w = gst[i];
-        st[i] = w;
-        sth[i] = cf{w.r * 0.5f, w.i * 0.5f};  // exact
-    }
-    if (need_windows) {
-        const float* gws = ws_src ? ws_src : t.ws;
-        for (int i = threadIdx.x; i < N; i += kBlock) {
-            wa[i] = t.wa[i];
-            ws[i] = gws[i];
-        }
-    }
-    __syncthreads();
-}
-
+// (kWaves / kBlock, the LDS carve `Lds`, load_tables and the any-size / streaming
+// argument structs: stream_common.h, shared with stream_spec.hip)
 
 // The same through a plain pointer and 64-bit indices (staged path).
 __device__ __forceinline__ float fetch_x64(const float* x, int64_t j, int64_t T, int mode) {
@@ -1458,64 +1422,7 @@ __global__ __launch_bounds__(kBlock) void k_cfft(const FftArgs a) {
 
 // ------------------------------------------------------------------ any size
 // General-size path (fft_any.h): one wave per frame / transform, two LDS
-// buffers of P elements per wave, tables read from global memory (L1/L2).
-struct AnyArgs {
-    DevTables t;
-    const float* twany;  // W_P^k, k < P
-    dev::any::Plan pl;
-    const float* in;
-    float* out;
-    float* spec;
-    int64_t ld_in, inc_in, ld_out, inc_out;  // FFT kernels
-    int64_t T, F;                            // synth kernel
-    int h, n_streams, batch, pad, pad_mode, waves_per_block;
-    int tw_len;  // float pairs in twany
-    float inv_n;
-};
-
-// LDS of the any-size kernels: [tw tw_len cf][st P cf][wa 2P f][per wave: 2 x P cf]
-struct AnyLds {
-    cf* tw;
-    cf* st;
-    float* wa;
-    cf* A;
-    cf* B;
-};
-
-template <bool LDS_TABLES>
-__device__ __forceinline__ AnyLds any_lds(const AnyArgs& a, bool need_wa) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int p = a.pl.p;
-    AnyLds l;
-    if constexpr (!LDS_TABLES) {  // large P: tables stay in global memory (L1/L2)
-        l.tw = const_cast<cf*>(reinterpret_cast<const cf*>(a.twany));
-        l.st = const_cast<cf*>(reinterpret_cast<const cf*>(a.t.st));
-        l.wa = const_cast<float*>(a.t.wa);
-        l.A = reinterpret_cast<cf*>(smem) + size_t(threadIdx.x >> 6) * 2 * p;
-        l.B = l.A + p;
-        return l;
-    }
-    l.tw = reinterpret_cast<cf*>(smem);
-    l.st = l.tw + a.tw_len;
-    l.wa = reinterpret_cast<float*>(l.st + p);
-    l.A = reinterpret_cast<cf*>(l.wa + 2 * p) + size_t(threadIdx.x >> 6) * 2 * p;
-    l.B = l.A + p;
-    const int nt = blockDim.x;
-    const cf* gtw = reinterpret_cast<const cf*>(a.twany);
-    const cf* gst = reinterpret_cast<const cf*>(a.t.st);
-    for (int i = threadIdx.x; i < a.tw_len; i += nt) l.tw[i] = gtw[i];
-    for (int i = threadIdx.x; i < p; i += nt) l.st[i] = gst[i];
-    if (need_wa)
-        for (int i = threadIdx.x; i < 2 * p; i += nt) l.wa[i] = a.t.wa[i];
-    __syncthreads();
-    return l;
-}
-
-static size_t any_lds_bytes(int p, int tw_len, int waves, bool tables) {
-    const size_t bufs = size_t(waves) * 2 * p * sizeof(cf);
-    return tables ? sizeof(cf) * (size_t(tw_len) + p) + sizeof(float) * 2 * p + bufs : bufs;
-}
-
+// buffers of P elements per wave (AnyArgs, any_lds: stream_common.h).
 // K_synth for any N: the push_frame_AoS input of every frame (and optionally the
 // forward spectrum), the same steps as k_synth_frames.
 template <bool HAS_GAIN, bool LDS_TABLES>
@@ -1653,74 +1560,11 @@ __global__ __launch_bounds__(1024) void k_stft_ola_any(const AnyFusedArgs f) {
     }
 }
 
-// K_stream_any: one hop of the per-hop streaming path for any N, H (DROP Framer).
-// Per channel: `hist` holds the last hl >= N + H samples (hop q at (qH) mod hl),
-// `acc` the OLA ring of rl = H ceil(N/H) floats.  When this hop completes frame
-// k (host-decided: wave-uniform), the frame runs through the same arithmetic as
-// K_fused_any and block k (H samples) is emitted.
-struct StreamAnyArgs {
-    AnyArgs a;                       // tables, plan, in (hop), out (hop), inv_n, h
-    float* hist;
-    float* acc;
-    int64_t in_ld, in_inc, out_ld, out_inc;
-    int64_t q, k;                    // hop index; frame completed by it (-1: none)
-    int channels, hl, rl, ring_len;
-    float gain;
-};
-
+// K_stream_any: one hop of the per-hop streaming path for any N, H (DROP Framer):
+// stream_common.h stream_any_body, the whole hop without a mask row.
 template <bool HAS_GAIN>
 __global__ __launch_bounds__(512) void k_stream_any(const StreamAnyArgs f) {
-    const AnyArgs& a = f.a;
-    const int p = a.pl.p, n = 2 * p, H = a.h;
-    const int lane = threadIdx.x & 63;
-    const AnyLds l = any_lds<true>(a, true);
-    const int wave = threadIdx.x >> 6;
-    float* ws = reinterpret_cast<float*>(l.A - size_t(wave) * 2 * p + size_t(a.waves_per_block) * 2 * p);
-    if (wave == 0)
-        for (int i = lane; i < n; i += 64) ws[i] = a.t.ws[i];
-    __syncthreads();
-    const int c = blockIdx.x * a.waves_per_block + wave;
-    if (c >= f.channels) return;
-    float* hist = f.hist + int64_t(c) * f.hl;
-    float* acc = f.acc + int64_t(c) * f.rl;
-    // store the hop
-    const int hb = int((f.q * H) % f.hl);
-    for (int i = lane; i < H; i += 64) hist[hb + i] = a.in[c * f.in_ld + i * f.in_inc];
-    if (f.k < 0) return;
-    __threadfence();  // the hop written by other lanes of this wave is read back below
-    const int64_t k = f.k;
-    const int fb = int((k * H) % f.hl);
-    cf* A = l.A;
-    cf* B = l.B;
-    for (int i = lane; i < p; i += 64) {
-        int j0 = fb + 2 * i, j1 = j0 + 1;
-        if (j0 >= f.hl) j0 -= f.hl;
-        if (j1 >= f.hl) j1 -= f.hl;
-        A[i] = {dev::sanit(hist[j0] * l.wa[2 * i]), dev::sanit(hist[j1] * l.wa[2 * i + 1])};
-    }
-    dev::wave_lds_fence();
-    cf* z = dev::any::fft<false>(A, B, a.pl, l.tw, lane);
-    cf* zo = z == A ? B : A;
-    dev::any::split_merge<HAS_GAIN>(z, zo, p, l.st, a.t.gain, nullptr, lane);
-    dev::wave_lds_fence();
-    const cf* r = dev::any::fft<true>(zo, z, a.pl, l.tw, lane);
-    const int nbr = f.rl / H;
-    const int rb = int(k % nbr) * H;
-    for (int i = lane; i < n; i += 64) {
-        const cf v = r[i >> 1];
-        const float src = dev::sanit(((i & 1) ? v.i : v.r) * a.inv_n);
-        int pos = rb + i;
-        if (pos >= f.rl) pos -= f.rl;
-        acc[pos] = __builtin_fmaf(__builtin_fmaf(src, ws[i], 0.0f), f.gain, acc[pos]);
-    }
-    __threadfence_block();
-    const int di = int((k * H) % f.ring_len);
-    for (int i = lane; i < H; i += 64) {
-        int d = di + i;
-        if (d >= f.ring_len) d -= f.ring_len;
-        a.out[c * f.out_ld + i * f.out_inc] = acc[rb + i] / a.t.den[d];
-        acc[rb + i] = 0.0f;
-    }
+    stream_any_body<kHopWhole, HAS_GAIN, false>(f, HopSpec{});
 }
 
 // batched IFftPlan::forward / inverse / forward_complex / inverse_complex, any size
@@ -1784,110 +1628,11 @@ __global__ __launch_bounds__(512) void k_fft_any(const AnyArgs a) {
 }
 
 // ------------------------------------------------------------------ streaming
-// One hop of the low-latency path (BASELINE config 4): per channel, the last
-// NB = N/H hops live in `hist` (slot q mod NB holds hop q) and the OLA
-// accumulator blocks in `acc` (slot b mod NB holds output block b).  Call q
-// (0-based) brings hop q; once q >= NB-1 the DROP-mode Framer yields frame
-// f = q-NB+1 (hops f..q), which goes through the same transform and OLA
-// arithmetic as the batched kernels; block f is then complete and emitted.
-// The lane that owns frame sample i owns it in every frame (H % 128 == 0), so a
-// lane only ever touches its own acc words: no cross-lane hazards.
-struct StreamArgs {
-    DevTables t;
-    const float* in;   // hop input: channel c sample i at in[c*in_ld + i*in_inc]
-    float* out;        // hop output, same layout (out_ld, out_inc)
-    float* hist;       // [C][N]
-    float* acc;        // [C][N]
-    int64_t in_ld, in_inc, out_ld, out_inc;
-    int64_t q;         // index of the hop being pushed
-    int channels, ring_len;
-    float inv_n, gain;
-};
-
+// K_stream_hop: one hop of the low-latency path (BASELINE config 4), one wave per
+// channel: stream_common.h stream_hop_body, the whole hop without a mask row.
 template <int E, int S, bool HAS_GAIN>
 __global__ __launch_bounds__(kBlock) void k_stream_hop(const StreamArgs a) {
-    constexpr int P = 64 * E, N = 2 * P, H = 128 * S, NB = E / S;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    cf* tw = reinterpret_cast<cf*>(smem);
-    cf* st = tw + P;
-    cf* sth = st + P;
-    float* wa = reinterpret_cast<float*>(sth + P);
-    float* ws = wa + N;
-    cf* bufs = reinterpret_cast<cf*>(ws + N);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int c = blockIdx.x * kWaves + wave;
-    const bool live = c < a.channels;
-    const int cc = live ? c : 0;
-    const float* in = a.in + cc * a.in_ld;
-    float* hist = a.hist + int64_t(cc) * N;
-    float* acc = a.acc + int64_t(cc) * N;
-    const int64_t q = a.q;
-    const bool frame = q >= NB - 1;
-    const int64_t f = q - (NB - 1);
-    // Everything a hop reads from global memory is requested before the table
-    // staging barrier, so the two latencies overlap (a hop is latency-bound).
-    float2 hop[S];
-#pragma unroll
-    for (int s2 = 0; s2 < S; ++s2) {
-        const int i0 = 2 * (lane + 64 * s2);
-        hop[s2] = make_float2(in[i0 * a.in_inc], in[(i0 + 1) * a.in_inc]);
-    }
-    float2 xv[E];      // frame samples (older hops from their slots, the new hop last)
-    float2 cur[E];     // OLA blocks this frame adds to
-    float2 dd[S];      // divisors of the block that completes
-#pragma unroll
-    for (int m = 0; m < E; ++m) {
-        const int i0 = 2 * (lane + 64 * m);
-        const int slot = int((f + m / S) % NB);
-        xv[m] = (frame && m < E - S) ? *reinterpret_cast<const float2*>(hist + slot * H + (i0 % H))
-                                     : make_float2(0.f, 0.f);
-        cur[m] = frame ? *reinterpret_cast<const float2*>(acc + slot * H + (i0 % H)) : make_float2(0.f, 0.f);
-    }
-#pragma unroll
-    for (int m = 0; m < S; ++m) {
-        const int64_t n = f * H + ((2 * (lane + 64 * m)) % H);
-        dd[m] = frame ? make_float2(a.t.den[n % a.ring_len], a.t.den[(n + 1) % a.ring_len]) : make_float2(1.f, 1.f);
-    }
-    load_tables<E>(a.t, tw, st, sth, wa, ws, true);
-    cf* buf = bufs + wave * xbuf_elems<P>();
-    if (!live) return;
-    if (frame) {
-        cf v[E];
-#pragma unroll
-        for (int m = 0; m < E; ++m) {
-            const int i0 = 2 * (lane + 64 * m);
-            const float2 x2 = m >= E - S ? hop[m - (E - S)] : xv[m];
-            v[m].r = dev::sanit(x2.x * wa[i0]);
-            v[m].i = dev::sanit(x2.y * wa[i0 + 1]);
-        }
-        dev::fft_wave<E, false>(v, buf, tw, lane);
-        dev::real_split_hook_merge<E, HAS_GAIN, false>(v, buf, st, sth, a.t.gain, lane);
-        dev::fft_wave<E, true>(v, buf, tw, lane);
-#pragma unroll
-        for (int m = 0; m < E; ++m) {
-            const int i0 = 2 * (lane + 64 * m);
-            const float o0 = dev::sanit(v[m].r * a.inv_n);
-            const float o1 = dev::sanit(v[m].i * a.inv_n);
-            const int slot = int((f + m / S) % NB);
-            float2* r = reinterpret_cast<float2*>(acc + slot * H + (i0 % H));
-            float2 cu = cur[m];
-            cu.x = __builtin_fmaf(__builtin_fmaf(o0, ws[i0], 0.0f), a.gain, cu.x);
-            cu.y = __builtin_fmaf(__builtin_fmaf(o1, ws[i0 + 1], 0.0f), a.gain, cu.y);
-            if (m < S) {  // block f is complete: produce(H) and clear its slot
-                const int pos = i0 % H;
-                float* o = a.out + c * a.out_ld;
-                o[pos * a.out_inc] = cu.x / dd[m].x;
-                o[(pos + 1) * a.out_inc] = cu.y / dd[m].y;
-                cu = make_float2(0.f, 0.f);
-            }
-            *r = cu;
-        }
-    }
-    // store the new hop into its slot for later frames
-    const int qslot = int(q % NB);
-#pragma unroll
-    for (int s2 = 0; s2 < S; ++s2)
-        *reinterpret_cast<float2*>(hist + qslot * H + 2 * (lane + 64 * s2)) = hop[s2];
+    stream_hop_body<E, S, kHopWhole, HAS_GAIN, false>(a, HopSpec{});
 }
 
 // ------------------------------------------------------------------ dispatch
@@ -2747,9 +2492,23 @@ hipError_t launch_stream_any(const Geometry& g, const DevTables& t, const float*
                              const float* in, int64_t in_ld, int64_t in_inc, float* out,
                              int64_t out_ld, int64_t out_inc, float* hist, float* acc, int channels,
                              int64_t q, int64_t k, hipStream_t stream) {
-    const int p = g.n / 2;
-    if (channels <= 0 || !any_supported(p)) return hipErrorInvalidValue;
     StreamAnyArgs f{};
+    size_t lds = 0;
+    if (!stream_any_args(g, t, twany, in, in_ld, in_inc, out, out_ld, out_inc, hist, acc, channels, q, k, f, lds))
+        return hipErrorInvalidValue;
+    const int w = f.a.waves_per_block;
+    auto kern = t.gain ? k_stream_any<true> : k_stream_any<false>;
+    hipError_t e = set_lds(kern, lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, dim3(unsigned((channels + w - 1) / w)), dim3(64 * w), lds, stream, f);
+    return hipGetLastError();
+}
+
+bool fk::stream_any_args(const Geometry& g, const DevTables& t, const float* twany, const float* in, int64_t in_ld,
+                         int64_t in_inc, float* out, int64_t out_ld, int64_t out_inc, float* hist, float* acc,
+                         int channels, int64_t q, int64_t k, StreamAnyArgs& f, size_t& lds) {
+    const int p = g.n / 2;
+    if (channels <= 0 || !any_supported(p)) return false;
     AnyArgs& a = f.a;
     a.t = t;
     a.twany = twany;
@@ -2775,14 +2534,10 @@ hipError_t launch_stream_any(const Geometry& g, const DevTables& t, const float*
     const size_t tables = sizeof(cf) * (size_t(a.tw_len) + p) + sizeof(float) * 4 * p;
     const size_t per_wave = sizeof(cf) * 2 * p;
     int w = int(std::min<size_t>(8, (150 * 1024 - std::min<size_t>(tables, 150 * 1024)) / per_wave));
-    if (w < 1) return hipErrorInvalidValue;
+    if (w < 1) return false;
     a.waves_per_block = w;
-    const size_t lds = tables + size_t(w) * per_wave;
-    auto kern = t.gain ? k_stream_any<true> : k_stream_any<false>;
-    hipError_t e = set_lds(kern, lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(unsigned((channels + w - 1) / w)), dim3(64 * w), lds, stream, f);
-    return hipGetLastError();
+    lds = tables + size_t(w) * per_wave;
+    return true;
 }
 
 bool fused_any_fits(int n, int h) {
@@ -3055,6 +2810,20 @@ hipError_t launch_stream_hop(const Geometry& g, const DevTables& t, const float*
                              float* hist, float* acc, int channels, int64_t q,
                              hipStream_t stream) {
     if (!fused_supported(g.n, g.h) || channels <= 0) return hipErrorInvalidValue;
+    const StreamArgs a = stream_hop_args(g, t, in, in_ld, in_inc, out, out_ld, out_inc, hist, acc, channels, q);
+    const int s = g.h / 128;
+    switch (e_of(g.n)) {
+        case 2: return stream_e<2>(s, a, stream);
+        case 4: return stream_e<4>(s, a, stream);
+        case 8: return stream_e<8>(s, a, stream);
+        case 16: return stream_e<16>(s, a, stream);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+StreamArgs fk::stream_hop_args(const Geometry& g, const DevTables& t, const float* in, int64_t in_ld, int64_t in_inc,
+                               float* out, int64_t out_ld, int64_t out_inc, float* hist, float* acc, int channels,
+                               int64_t q) {
     StreamArgs a;
     a.t = t;
     a.in = in;
@@ -3070,14 +2839,7 @@ hipError_t launch_stream_hop(const Geometry& g, const DevTables& t, const float*
     a.ring_len = g.ring_len;
     a.inv_n = g.inv_n;
     a.gain = g.gain;
-    const int s = g.h / 128;
-    switch (e_of(g.n)) {
-        case 2: return stream_e<2>(s, a, stream);
-        case 4: return stream_e<4>(s, a, stream);
-        case 8: return stream_e<8>(s, a, stream);
-        case 16: return stream_e<16>(s, a, stream);
-        default: return hipErrorInvalidValue;
-    }
+    return a;
 }
 
 hipError_t launch_rfft(const Geometry& g, const DevTables& t, const float* in, float* out,

@@ -156,6 +156,53 @@ int main(int argc, char** argv) {
     HIPCHECK(hipStreamSynchronize(s));
     const double b2b = std::chrono::duration<double>(clk::now() - tb).count();
 
+    // the hop with a spectral step, same method (pass 0 warms up): masked_hop =
+    // crlot_stream_push_hop_masked with a per-channel row, split_hop =
+    // crlot_stream_stft_hop + crlot_stream_istft_hop back to back (two launches,
+    // the spectra through HBM).  The rows are ones, so both must give push_hop's bits.
+    const int64_t bins = N / 2 + 1, ld_spec = 2 * bins;
+    float *d_mask, *d_spec;
+    HIPCHECK(hipMalloc(&d_mask, sizeof(float) * size_t(C) * bins));
+    HIPCHECK(hipMalloc(&d_spec, sizeof(float) * size_t(C) * ld_spec));
+    {
+        std::vector<float> ones(size_t(C) * bins, 1.0f);
+        HIPCHECK(hipMemcpy(d_mask, ones.data(), sizeof(float) * ones.size(), hipMemcpyHostToDevice));
+    }
+    Stat mw, md, sw, sd;
+    int64_t spec_mismatches = 0;
+    std::vector<float> got(hop_floats);
+    for (int form = 0; form < 2; ++form) {
+        for (int pass = 0; pass < 2; ++pass) {
+            CRCHECK(crlot_stream_reset(st));
+            for (int q = 0; q < hops; ++q) {
+                int32_t em = 0;
+                auto t0 = clk::now();
+                HIPCHECK(hipEventRecord(e0, s));
+                if (form == 0) {
+                    CRCHECK(crlot_stream_push_hop_masked(st, d_in + q * hop_floats, d_mask, bins, d_out, &em, s));
+                } else {
+                    CRCHECK(crlot_stream_stft_hop(st, d_in + q * hop_floats, d_spec, ld_spec, &em, s));
+                    if (em) CRCHECK(crlot_stream_istft_hop(st, d_spec, ld_spec, nullptr, 0, d_out, s));
+                }
+                HIPCHECK(hipEventRecord(e1, s));
+                HIPCHECK(hipStreamSynchronize(s));
+                auto t1 = clk::now();
+                float ms;
+                HIPCHECK(hipEventElapsedTime(&ms, e0, e1));
+                if (pass == 1 && em) {
+                    (form == 0 ? mw : sw).add(std::chrono::duration<double, std::micro>(t1 - t0).count());
+                    (form == 0 ? md : sd).add(ms * 1e3);
+                    HIPCHECK(hipMemcpy(got.data(), d_out, sizeof(float) * hop_floats, hipMemcpyDeviceToHost));
+                    if (std::memcmp(got.data(), ref.data() + q * hop_floats, sizeof(float) * hop_floats))
+                        ++spec_mismatches;
+                }
+            }
+        }
+    }
+    CRCHECK(crlot_stream_reset(st));
+    HIPCHECK(hipFree(d_mask));
+    HIPCHECK(hipFree(d_spec));
+
     // resident kernel, hops in host memory (crlot_stream_rt_push_hop: copy in,
     // doorbell, wait, copy out), then the zero-copy form (caller writes the slot)
     crlot_stream_rt* rt;
@@ -240,6 +287,11 @@ int main(int argc, char** argv) {
     print_stat("push_hop_device_buffers_wall_us", dw);
     print_stat("push_hop_event_us", dd);
     std::printf("\"back_to_back_us_per_hop\": %.2f, ", b2b / hops * 1e6);
+    print_stat("masked_hop_wall_us", mw);
+    print_stat("masked_hop_event_us", md);
+    print_stat("split_hop_wall_us", sw);
+    print_stat("split_hop_event_us", sd);
+    std::printf("\"spectral_hop_bit_mismatches_vs_push_hop\": %lld, ", (long long)spec_mismatches);
     print_stat("resident_push_hop_host_buffers_wall_us", rw);
     print_stat("resident_device_us", rd);
     print_stat("resident_zero_copy_interleaved_caller_wall_us", zw);
@@ -249,7 +301,7 @@ int main(int argc, char** argv) {
                 piped / hops * 1e6, double(hops) * H / 48000.0 / piped, (long long)mismatches);
     std::fprintf(stderr, "phases_ns_wg0_last_hop: %.0f %.0f %.0f %.0f %.0f %.0f %.0f\n", ph[0], ph[1], ph[2], ph[3],
                  ph[4], ph[5], ph[6]);
-    if (mismatches) return 4;
+    if (mismatches || spec_mismatches) return 4;
     crlot_stream_destroy(st);
     crlot_plan_destroy(plan);
     return 0;

@@ -330,8 +330,10 @@ int crlot_ola_gather(crlot_plan* plan, const float* d_frames, float* d_y, int32_
  * (NULL); it must hold a row for every frame those calls run.  With a mask,
  * crlot_roundtrip(x) equals crlot_istft_ola(crlot_stft(x)) bit for bit (one
  * walk over HBM where the shape allows it: power-of-two N, H % 128 == 0,
- * N % H == 0, 8-byte aligned output rows).  The streaming objects, the host-pointer
- * calls and crlot_roundtrip_stages keep the per-bin gain only. */
+ * N % H == 0, 8-byte aligned output rows).  The per-hop streaming object takes
+ * its mask a row per call (crlot_stream_push_hop_masked, crlot_stream_istft_hop)
+ * and never reads the plan's; the resident crlot_stream_rt, the host-pointer calls
+ * and crlot_roundtrip_stages keep the per-bin gain only. */
 int crlot_plan_set_spectral_mask(crlot_plan* plan, const float* d_mask, int64_t ld_frame, int64_t ld_stream);
 int crlot_stft(crlot_plan* plan, const float* d_x, float* d_spec, int32_t n_streams, int64_t T, int64_t ld_x,
                int64_t ld_spec, int64_t ld_frame, void* stream);
@@ -425,6 +427,46 @@ int crlot_stream_reset(crlot_stream* st);
 int crlot_stream_set_layout(crlot_stream* st, int32_t interleaved);
 int crlot_stream_push_hop(crlot_stream* st, const float* d_hop_in, float* d_hop_out,
                           int32_t* emitted, void* stream);
+
+/* The per-hop path with a time-varying spectral step (a suppressor, a Wiener
+ * gain, a mask model that looks at frame k and edits frame k before it is
+ * synthesised): the hop cut at its spectrum, and the hop with a mask row.
+ * Numerics are the batched entries', operation for operation (crlot_stft,
+ * crlot_istft_ola, crlot_roundtrip with a mask): sanitize(x * wa), forward,
+ * kiss_fftr split; the step (X * gain) * mask in float32 on re and im each;
+ * kiss_fftri merge, * 1/N, sanitize, fma(fma(o, ws, 0), g, acc), IEEE / den.
+ * Spectra are channel-major whatever the PCM layout: channel c's N/2+1 float
+ * pairs at d_spec[c*ld_spec + 2*b], ld_spec even and >= N + 2, d_spec 8-byte
+ * aligned; DC / Nyquist imaginary parts are 0 on the way out and ignored on the
+ * way in.  A mask row holds N/2+1 real floats, channel c's at d_mask[c*ld_mask];
+ * ld_mask = 0 shares one row across the channels, otherwise ld_mask >= N/2+1;
+ * d_mask = NULL: no mask.  Violations are CRLOT_EINVAL.
+ *   stft_hop         the analysis half of push_hop: consume H samples per channel
+ *                    (layout as push_hop); when the hop completes DROP frame f,
+ *                    write its spectrum -- frame * analysis window ->
+ *                    IFftPlan::forward, BEFORE the gain: crlot_stft's row f.
+ *                    *emitted = 1 if a spectrum was written, else 0 (d_spec untouched).
+ *   istft_hop        the synthesis half: one spectrum per channel -> (X * gain) *
+ *                    mask row (either may be absent) -> IFftPlan::inverse ->
+ *                    push_frame_AoS(k*H) -> produce(H): always writes block k (H
+ *                    samples per channel, hop layout), k = istft_hop calls so far.
+ *   push_hop_masked  push_hop with a mask row for the frame this hop completes
+ *                    (read only on a hop that emits): one launch, no spectra in
+ *                    HBM; equal bit for bit to istft_hop(stft_hop(hop)), and to
+ *                    push_hop with a row of ones or d_mask = NULL.
+ * An object's first call after create / reset fixes its mode: whole (push_hop and
+ * push_hop_masked, freely mixed) or split (stft_hop and istft_hop, whose two
+ * halves keep independent counters -- hops analysed, frames synthesised -- and
+ * share nothing but the plan and the object).  A call of the other mode is
+ * CRLOT_ERUNTIME until crlot_stream_reset, which clears both counters and the
+ * mode.  The hop / frame index is a by-value kernel argument, so a captured
+ * graph of one hop replays that hop: capture is not supported on this path. */
+int crlot_stream_stft_hop(crlot_stream* st, const float* d_hop_in, float* d_spec, int64_t ld_spec,
+                          int32_t* emitted, void* stream);
+int crlot_stream_istft_hop(crlot_stream* st, const float* d_spec, int64_t ld_spec, const float* d_mask,
+                           int64_t ld_mask, float* d_hop_out, void* stream);
+int crlot_stream_push_hop_masked(crlot_stream* st, const float* d_hop_in, const float* d_mask, int64_t ld_mask,
+                                 float* d_hop_out, int32_t* emitted, void* stream);
 
 /* ---------------------------------------------------------------- resident streaming
  * The same per-hop contract as crlot_stream_* (DROP Framer fed H samples per

@@ -234,6 +234,52 @@ class RealtimeStream {
     crlot_stream_rt* st_ = nullptr;
 };
 
+// Per-hop streaming with hops in DEVICE memory and a time-varying spectral step:
+// the per-launch object behind crlot_stream_* (one kernel launch per call on
+// `stream`).  push_hop / push_hop_masked are the whole hop (a mask row of N/2+1
+// real floats per channel for the frame the hop completes; ld_mask 0 shares one
+// row); stft_hop / istft_hop are its two halves with the spectra -- channel-major
+// rows of N/2+1 float pairs, ld_spec floats apart -- in the caller's hands.  An
+// object runs whole or split, fixed by its first call until reset().
+class SpectralStream {
+   public:
+    SpectralStream(const StftEngine& eng, int channels, bool interleaved = false) {
+        check(crlot_stream_create(eng.plan(), channels, &st_), "crlot_stream_create");
+        check(crlot_stream_set_layout(st_, interleaved ? 1 : 0), "crlot_stream_set_layout");
+    }
+    ~SpectralStream() { crlot_stream_destroy(st_); }
+    SpectralStream(const SpectralStream&) = delete;
+    SpectralStream& operator=(const SpectralStream&) = delete;
+    // each returns the samples (push_hop*: 0 or H) or spectra (stft_hop: 0 or 1) written per channel
+    size_t push_hop(const float* d_hop_in, float* d_hop_out, void* stream = nullptr) {
+        int32_t em = 0;
+        check(crlot_stream_push_hop(st_, d_hop_in, d_hop_out, &em, stream), "crlot_stream_push_hop");
+        return size_t(em);
+    }
+    size_t push_hop_masked(const float* d_hop_in, const float* d_mask, int64_t ld_mask, float* d_hop_out,
+                           void* stream = nullptr) {
+        int32_t em = 0;
+        check(crlot_stream_push_hop_masked(st_, d_hop_in, d_mask, ld_mask, d_hop_out, &em, stream),
+              "crlot_stream_push_hop_masked");
+        return size_t(em);
+    }
+    size_t stft_hop(const float* d_hop_in, float* d_spec, int64_t ld_spec, void* stream = nullptr) {
+        int32_t em = 0;
+        check(crlot_stream_stft_hop(st_, d_hop_in, d_spec, ld_spec, &em, stream), "crlot_stream_stft_hop");
+        return size_t(em);
+    }
+    void istft_hop(const float* d_spec, int64_t ld_spec, const float* d_mask, int64_t ld_mask, float* d_hop_out,
+                   void* stream = nullptr) {
+        check(crlot_stream_istft_hop(st_, d_spec, ld_spec, d_mask, ld_mask, d_hop_out, stream),
+              "crlot_stream_istft_hop");
+    }
+    void reset() { check(crlot_stream_reset(st_), "crlot_stream_reset"); }
+    crlot_stream* handle() const { return st_; }
+
+   private:
+    crlot_stream* st_ = nullptr;
+};
+
 // io/wav.h WavReader / WavWriter (same methods; open() returns false on a
 // file the reference would reject, crlot_last_error() says why).
 namespace io {
