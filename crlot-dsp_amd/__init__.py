@@ -347,6 +347,47 @@ def _ld(t, dim: int, minimum: int) -> int:
     return int(t.stride(dim)) if t.shape[dim] > 1 else int(minimum)
 
 
+def mask_layout(shape, strides, dtype: str, device_index, plan_device: int, bins: int):
+    """Validate a spectral mask from its plain description -- shape and strides (in
+    elements) as tuples, dtype name, device index (None: not a device tensor) -- for a
+    plan on `plan_device` with `bins` = N/2+1.  Returns (ld_frame, ld_stream,
+    (S_mask or None, F_mask)): the leading dimensions the kernels index with and the
+    extent later calls are checked against.  S_mask is None when one set of rows
+    serves every stream: a (F, bins) mask, or (1, F, bins), whose stream stride is 0.
+    Everything the kernels would read out of bounds is refused here."""
+    shape, strides = tuple(int(v) for v in shape), tuple(int(v) for v in strides)
+    if len(shape) not in (2, 3) or len(strides) != len(shape) or shape[-1] != bins or strides[-1] != 1:
+        raise ValueError("mask must be a (S, F, N/2+1) or (F, N/2+1) device tensor with contiguous rows")
+    if dtype != "float32":
+        raise ValueError(f"mask must be float32, not {dtype}")
+    if device_index is None or int(device_index) != int(plan_device):
+        raise ValueError(f"mask must live on the plan's device {plan_device}, not "
+                         f"{'the host' if device_index is None else device_index}")
+    if min(shape) < 1:
+        raise ValueError("mask has an empty dimension")
+    F_mask = shape[-2]
+    # a size-1 dim's stride is meaningless: the dense value there
+    ld_frame = strides[-2] if F_mask > 1 else bins
+    if ld_frame < 0 or strides[0] < 0:
+        raise ValueError("mask strides must not be negative")
+    if len(shape) == 2 or shape[0] == 1:
+        return ld_frame, 0, (None, F_mask)
+    return ld_frame, strides[0], (shape[0], F_mask)
+
+
+def check_mask_extent(extent, n_streams: int, n_frames: int, what: str = "call"):
+    """Raise ValueError when the stored mask (extent = (S_mask or None, F_mask) from
+    mask_layout, None: no mask) has fewer frames or streams than a call of
+    n_streams x n_frames reads."""
+    if extent is None:
+        return
+    s_mask, f_mask = extent
+    if n_frames > f_mask:
+        raise ValueError(f"{what}: the spectral mask has {f_mask} frames, the call has {n_frames}")
+    if s_mask is not None and n_streams > s_mask:
+        raise ValueError(f"{what}: the spectral mask has {s_mask} streams, the call has {n_streams}")
+
+
 def _stream_handle(tensor) -> int:
     torch = _torch()
     return int(torch.cuda.current_stream(tensor.device).cuda_stream)
@@ -389,6 +430,7 @@ class Plan:
         h = C.c_void_p()
         _check(lib().crlot_plan_create(C.byref(d), C.byref(h)), "crlot_plan_create")
         self._h = h
+        self._mask, self._mask_extent = None, None
         n, hop, ring = C.c_int32(), C.c_int32(), C.c_int32()
         _check(lib().crlot_plan_info(self._h, C.byref(n), C.byref(hop), C.byref(ring)))
         self.frame_size, self.hop_size, self.ring_len = n.value, hop.value, ring.value
@@ -424,10 +466,14 @@ class Plan:
         s = self._cur_stream() if stream is None else stream
         _check(lib().crlot_plan_reserve_stream(self._h, n_streams, T, channels, s), "reserve_stream")
 
+    def _device_index(self) -> int:
+        return self.cfg.device if self.cfg.device >= 0 else _torch().cuda.current_device()
+
     def _cur_stream(self) -> int:
-        torch = _torch()
-        dev = self.cfg.device if self.cfg.device >= 0 else torch.cuda.current_device()
-        return int(torch.cuda.current_stream(dev).cuda_stream)
+        return int(_torch().cuda.current_stream(self._device_index()).cuda_stream)
+
+    def _require_mask_covers(self, n_streams: int, n_frames: int, what: str):
+        check_mask_extent(getattr(self, "_mask_extent", None), n_streams, n_frames, what)
 
     def upload_tables(self, window=None, norm=None):
         """Replace window / norm, ordered on the current torch stream."""
@@ -471,19 +517,19 @@ class Plan:
 
     def set_spectral_mask(self, mask=None):
         """Time-varying spectral step (crlot_plan_set_spectral_mask): mask is a
-        float32 device tensor (S, F, N/2+1) -- one real row per stream and frame --
-        or (F, N/2+1), one row per frame shared by every stream; None clears it.
-        The plan keeps a reference to the tensor until it is replaced."""
+        float32 tensor on the plan's device, (S, F, N/2+1) -- one real row per stream
+        and frame -- or (F, N/2+1) / (1, F, N/2+1), one row per frame shared by every
+        stream; None clears it.  The plan keeps a reference to the tensor until it is
+        replaced, and a later call with more frames or streams than the mask has
+        raises ValueError before anything is launched."""
         if mask is None:
-            self._mask = None
+            self._mask, self._mask_extent = None, None
             _check(lib().crlot_plan_set_spectral_mask(self._h, None, 0, 0), "crlot_plan_set_spectral_mask")
             return
-        bins = self.frame_size // 2 + 1
-        if not mask.is_cuda or mask.shape[-1] != bins or mask.stride(-1) != 1 or mask.dim() not in (2, 3):
-            raise ValueError("mask must be a (S, F, N/2+1) or (F, N/2+1) device tensor with contiguous rows")
-        ld_frame = _ld(mask, -2, bins)
-        ld_stream = 0 if mask.dim() == 2 else _ld(mask, 0, mask.shape[1] * ld_frame)
-        self._mask = mask
+        ld_frame, ld_stream, extent = mask_layout(
+            tuple(mask.shape), tuple(mask.stride()), str(mask.dtype).replace("torch.", ""),
+            mask.device.index if mask.is_cuda else None, self._device_index(), self.frame_size // 2 + 1)
+        self._mask, self._mask_extent = mask, extent
         _check(lib().crlot_plan_set_spectral_mask(self._h, mask.data_ptr(), ld_frame, ld_stream),
                "crlot_plan_set_spectral_mask")
 
@@ -516,6 +562,7 @@ class Plan:
         if spec.dtype != torch.complex64 or not spec.is_cuda or bins != self.frame_size // 2 + 1 or \
                 spec.stride(2) != 1:
             raise ValueError("spec must be (S, F, N/2+1) complex64 with contiguous rows")
+        self._require_mask_covers(S, F, "istft_ola")
         L = F * self.hop_size
         if y is None:
             y = torch.empty((S, L), dtype=torch.float32, device=spec.device)
@@ -538,6 +585,7 @@ class Plan:
         if x.stride(1) != 1:
             raise ValueError("x rows must be contiguous")
         L = self.output_length(T)
+        self._require_mask_covers(S, self.frame_count(T), "roundtrip")
         if y is None:
             y = torch.empty((S, L), dtype=torch.float32, device=x.device)
         if y.shape[0] != S or y.shape[1] < L or y.stride(1) != 1:
@@ -555,6 +603,8 @@ class Plan:
         if x.stride(2) != 1 or x.stride(1) != Cc:
             raise ValueError("x must be (G, T, C) with contiguous rows of C samples")
         L = self.output_length(T)
+        # every channel is a stream of its own: the mask is read for G * C streams
+        self._require_mask_covers(G * Cc, self.frame_count(T), "roundtrip_interleaved")
         if y is None:
             y = torch.empty((G, L, Cc), dtype=torch.float32, device=x.device)
         s = _stream_handle(x) if stream is None else stream

@@ -174,6 +174,64 @@ __device__ __forceinline__ uint32_t hop_ok_bits(const float* h, uint32_t lo_bits
     return __builtin_amdgcn_ballot_w64((mx > hi_bits) | (mn < lo_bits - 1u)) == 0 ? 1u : 0u;
 }
 
+// The regime verdict of the spectral pair walkers' inverse side (K_pair_istft,
+// K_pair_mask) for frames (a, b) sharing one complex transform.  The pair leaves
+// the paired regime when a stepped value is non-finite or huge (`bad`), and also
+// when exactly ONE member is all zero -- a gated frame next to a live one: in
+// the shared transform the zero member would inherit ~eps |mate| of rounding
+// noise, inverted alone it is exact zeros, as the reference's per-frame inverse
+// gives.  (Both zero: the transform of zeros is zeros.  Frame b past the last
+// frame is no member: the pair stays as it was.)  live_a / live_b: this lane
+// holds a non-zero stepped value (istft) or step multiplier (mask) of frame a / b.
+// The code is wave-uniform; a workgroup ORs its waves' codes.  L < 64: the wave
+// walks 64 / L streams side by side, and one of them with a lone silent member
+// sends the whole wave to the per-frame regime (as its other verdicts do).
+constexpr uint32_t kPairBad = 1u, kPairLiveA = 2u, kPairLiveB = 4u, kPairLone = 8u;
+template <int L = 64>
+__device__ __forceinline__ uint32_t pair_code(bool bad, bool live_a, bool live_b) {
+    static_assert(L == 64 || L == 32, "a wave, or its two halves");
+    const uint64_t la = __builtin_amdgcn_ballot_w64(live_a), lb = __builtin_amdgcn_ballot_w64(live_b);
+    uint32_t c = __builtin_amdgcn_ballot_w64(bad) != 0 ? kPairBad : 0u;
+    if constexpr (L == 64) {
+        c |= (la != 0 ? kPairLiveA : 0u) | (lb != 0 ? kPairLiveB : 0u);
+    } else {
+        const bool lo = (uint32_t(la) != 0u) != (uint32_t(lb) != 0u);
+        const bool hi = (uint32_t(la >> 32) != 0u) != (uint32_t(lb >> 32) != 0u);
+        c |= (lo | hi) ? kPairLone : 0u;
+    }
+    return c;
+}
+__device__ __forceinline__ bool pair_code_paired(uint32_t code, bool has_b) {
+    const bool lone = (code & kPairLone) != 0u || ((code & kPairLiveA) != 0u) != ((code & kPairLiveB) != 0u);
+    return (code & kPairBad) == 0u && !(lone && has_b);
+}
+
+// The forward side of the same rule (K_pair_stft, K_pair_mask): a pair with exactly
+// one all-zero INPUT frame -- exact silence next to an onset -- is transformed
+// frame by frame, so the silent frame's spectrum is exact zeros instead of
+// ~eps |mate's spectrum|, which a mask that attenuates the mate would not shrink.
+// any_nonzero: this lane holds a value that is not +-0 among f[0 .. n) (the bit
+// patterns ORed, one v_or3 per two values; NaN counts as non-zero).
+// hop_live: 1 when any sample of the hop (SH per lane, whole wave) is non-zero;
+// the walkers keep these bits beside hop_ok's, bit h for hop k + h of the pair at k.
+template <int n>
+__device__ __forceinline__ bool any_nonzero(const float* f) {
+    uint32_t u = 0u;
+#pragma unroll
+    for (int q = 0; q < n; ++q) u |= __builtin_bit_cast(uint32_t, f[q]);
+    return (u & 0x7fffffffu) != 0u;
+}
+template <int SH>
+__device__ __forceinline__ uint32_t hop_live(const float* h) {
+    return __builtin_amdgcn_ballot_w64(any_nonzero<SH>(h)) != 0 ? 1u : 0u;
+}
+// the pair code's liveness bits from them: frame a = hops 0 .. NB-1, frame b = hops 1 .. NB
+template <int NB>
+__device__ __forceinline__ uint32_t hops_live_code(uint32_t live) {
+    constexpr uint32_t fa = (1u << NB) - 1u;
+    return ((live & fa) != 0u ? kPairLiveA : 0u) | ((live & (fa << 1)) != 0u ? kPairLiveB : 0u);
+}
+
 // den / rden of OLA block b for this lane (DevTables::pden: [block][lane][den SH | rden SH]).
 template <int SH>
 __device__ __forceinline__ void load_den(float (&dr)[2 * SH], __amdgpu_buffer_rsrc_t rp, int lane, int b) {

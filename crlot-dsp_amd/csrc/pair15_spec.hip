@@ -178,6 +178,13 @@ __device__ __forceinline__ bool q15_ok(const float (&f)[kQE], float lo, float hi
     }
     return __builtin_amdgcn_ballot_w64(bad) == 0;
 }
+// true when, in each half's stream (L = 32) or the wave's (L = 64), the input frames a and b
+// are both all zero or both hold a non-zero sample: a lone all-zero frame is transformed
+// alone (exact zeros; pair_code, fused_common.h)
+template <int L>
+__device__ __forceinline__ bool q15_no_lone_silent(const float (&fa)[kQE], const float (&fb)[kQE]) {
+    return pair_code_paired(pair_code<L>(false, any_nonzero<kQE>(fa), any_nonzero<kQE>(fb)), true);
+}
 // Z[-k] of registers d = 0 .. 15 (the partner half-lane's register 15 - d; half-lane 0: its own (16 - d) mod 16)
 __device__ __forceinline__ void q15_partners(const dev::pc (&v)[16], dev::pc (&zp)[16], bool self, int partner_lane) {
 #pragma unroll
@@ -330,7 +337,7 @@ __global__ __launch_bounds__(64 * kQW, 2) void k_p15_stft(const PairSpecArgs pa)
         const bool two = k + 1 < w.f1;
         float* ra = so + int64_t(k) * pa.ld_frame;
         float* rb = ra + pa.ld_frame;
-        const bool paired = q15_ok(fa, xlo, xhi) && q15_ok(fb, xlo, xhi);
+        const bool paired = q15_ok(fa, xlo, xhi) && q15_ok(fb, xlo, xhi) && (!two || q15_no_lone_silent<L>(fa, fb));
         dev::pc v[16];
         if (paired) {
 #pragma unroll
@@ -419,8 +426,11 @@ __global__ __launch_bounds__(64 * kQW, 2) void k_p15_istft(const PairSpecArgs pa
             }
         }
     };
-    auto stage = [&]() -> bool {
+    // true when the pair keeps the paired regime (a lone all-zero member of either half's
+    // stream is done alone: pair_code, fused_common.h)
+    auto stage = [&](bool has_b) -> bool {
         bool bad = false;
+        float peak_a = 0.0f, peak_b = 0.0f;  // (this lane's max |value| of frame a / b; a NaN is `bad`)
 #pragma unroll
         for (int i = 0; i < MI; ++i) {
             const int kr = hl + L * i;
@@ -434,15 +444,18 @@ __global__ __launch_bounds__(64 * kQW, 2) void k_p15_istft(const PairSpecArgs pa
                     by *= mb_[i];
                 }
                 if (kr == 0 || kr == P2) ay = by = 0.0f;
-                const float mx = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(ax), __builtin_fabsf(ay)),
-                                                 __builtin_fmaxf(__builtin_fabsf(bx), __builtin_fabsf(by)));
+                const float m_a = __builtin_fmaxf(__builtin_fabsf(ax), __builtin_fabsf(ay));
+                const float m_b = __builtin_fmaxf(__builtin_fabsf(bx), __builtin_fabsf(by));
+                const float mx = __builtin_fmaxf(m_a, m_b);
+                peak_a = __builtin_fmaxf(peak_a, m_a);
+                peak_b = __builtin_fmaxf(peak_b, m_b);
                 bad |= !(mx <= 0x1p60f) | (ax != ax) | (ay != ay) | (bx != bx) | (by != by);  // (NaN, Inf, huge)
                 sbuf[kr] = dev::pc_mk(ax, ay);
                 sbuf[OB + kr] = dev::pc_mk(bx, by);
             }
         }
         dev::wave_lds_fence();
-        return __builtin_amdgcn_ballot_w64(bad) == 0;
+        return pair_code_paired(pair_code<L>(bad, peak_a != 0.0f, peak_b != 0.0f), has_b);
     };
     // bin kb of (lane, d): real bin kb (kb <= N/2) or N - kb conjugated; the zero row stays 0
     auto gather = [&](dev::pc (&v)[16], bool pair_form, int off) {
@@ -467,7 +480,7 @@ __global__ __launch_bounds__(64 * kQW, 2) void k_p15_istft(const PairSpecArgs pa
         dev::pc v[16];
         const bool more = k + 2 < w.f1;
         if (!PF) load_rows(k);
-        if (stage()) {
+        if (stage(k + 1 < a.F)) {
             gather(v, true, 0);
             G::inv(v, buf, tw, lane);
             if (PF && more) load_rows(k + 2);  // (in flight during the OLA stage)
@@ -478,7 +491,7 @@ __global__ __launch_bounds__(64 * kQW, 2) void k_p15_istft(const PairSpecArgs pa
             ola.template push<false>(v, wsg, a.inv_n, k);
             ola.produce(k);
             if (k + 1 < w.f1) {
-                (void)stage();
+                (void)stage(true);
                 gather(v, false, OB);
                 G::inv(v, buf, tw, lane);
                 ola.template push<false>(v, wsg, a.inv_n, k + 1);
@@ -523,23 +536,32 @@ __global__ __launch_bounds__(64 * kQW, 2) void k_p15_mask(const PairSpecArgs pa)
     const float* mrow0 = pa.mask.p + int64_t(w.s) * pa.mask.ld_stream;
     auto row_a = [&](int k) { return mrow0 + int64_t(k) * pa.mask.ld_frame; };
     auto row_b = [&](int k) { return k + 1 < a.F ? row_a(k) + pa.mask.ld_frame : row_a(k); };  // (past F: unused)
-    float ma[MI], mb[MI];  // the pair's mask rows by real bin h + L i (<= N/2; 1 beyond)
+    float ma[MI], mb[MI];  // the pair's mask rows by real bin h + L i (<= N/2; 0 beyond: unused by the step, silent in its verdict)
     auto load_rows = [&](int k) {
         const float* r0 = row_a(k);
         const float* r1 = row_b(k);
 #pragma unroll
         for (int i = 0; i < MI; ++i) {
             const int kr = hl + L * i;
-            ma[i] = kr <= P2 ? r0[kr] : 1.0f;
-            mb[i] = kr <= P2 ? r1[kr] : 1.0f;
+            ma[i] = kr <= P2 ? r0[kr] : 0.0f;
+            mb[i] = kr <= P2 ? r1[kr] : 0.0f;
         }
     };
+    // true: every value keeps the paired regime, and in neither half's stream is a lone
+    // member's multiplier row g m all zero (a gated frame next to an open one is done
+    // alone: exact zeros; pair_code, fused_common.h; row b past F is row a again)
     auto rows_ok = [&]() {
         bool bad = false;
+        float peak_a = 0.0f, peak_b = 0.0f;  // (this lane's max |value| of frame a / b; a NaN is `bad`)
 #pragma unroll
-        for (int i = 0; i < MI; ++i)
+        for (int i = 0; i < MI; ++i) {
+            const int kr = hl + L * i;
             bad |= !(__builtin_fabsf(ma[i]) <= 0x1p20f) | !(__builtin_fabsf(mb[i]) <= 0x1p20f);  // (NaN too)
-        return __builtin_amdgcn_ballot_w64(bad) == 0;
+            const float g = kr <= P2 && a.t.gain ? a.t.gain[kr] : 1.0f;
+            peak_a = __builtin_fmaxf(peak_a, __builtin_fabsf(g * ma[i]));  // (beyond N/2: zeros)
+            peak_b = __builtin_fmaxf(peak_b, __builtin_fabsf(g * mb[i]));
+        }
+        return pair_code_paired(pair_code<L>(bad, peak_a != 0.0f, peak_b != 0.0f), true);
     };
     float fa[E], fb[E];
     auto load = [&](float (&f)[E], int k) { q15_load<L>(f, rx, hl, w.xo, k * H - a.pad, a.T, a.pad_mode); };
@@ -547,8 +569,9 @@ __global__ __launch_bounds__(64 * kQW, 2) void k_p15_mask(const PairSpecArgs pa)
     load(fb, w.fs + 1);
     load_rows(w.fs);
     for (int k = w.fs; k < w.f1; k += 2) {
-        const bool paired = q15_ok(fa, xlo, xhi) && q15_ok(fb, xlo, xhi) && rows_ok();
         const bool partner_frame = k + 1 < a.F;  // frame k+1 past the last: imaginary part 0
+        const bool paired = q15_ok(fa, xlo, xhi) && q15_ok(fb, xlo, xhi) && rows_ok() &&
+                            (!partner_frame || q15_no_lone_silent<L>(fa, fb));
         dev::pc v[16];
         if (paired) {
 #pragma unroll

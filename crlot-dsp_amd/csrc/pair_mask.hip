@@ -174,11 +174,12 @@ __global__ __launch_bounds__(64 * kMW, CRLOT_PAIR_MASK_WAVES) void k_pair_mask(c
         for (int q = 0; q < SH; ++q) acc[NB - 1][q] = 0.f;
     };
 
-    uint32_t hopok = 0;
+    uint32_t hopok = 0, hoplive = 0;  // (hoplive: the hop holds a non-zero sample, hop_live)
 #pragma unroll
     for (int h = 0; h <= NB; ++h) {
         load_hop(xin + h * SH, (fs + h) * H - a.pad);
         hopok |= hop_ok<SH>(xin + h * SH, xlo, xhi) << h;
+        hoplive |= hop_live<SH>(xin + h * SH) << h;
     }
 #pragma unroll
     for (int j = 0; j < NB; ++j)
@@ -206,17 +207,22 @@ __global__ __launch_bounds__(64 * kMW, CRLOT_PAIR_MASK_WAVES) void k_pair_mask(c
             mrb[i] = rb[kr];
         }
     };
-    auto stage_rows = [&]() -> bool {  // true: every value keeps the paired regime
+    // true: every value keeps the paired regime, and no lone member's multipliers g m are all zero
+    // (a gated frame next to an open one is done alone: exact zeros; pair_code, fused_common.h)
+    auto stage_rows = [&]() -> bool {
         bool bad = false;
+        float peak_a = 0.0f, peak_b = 0.0f;  // (max |g m| of frame a / b in this lane)
 #pragma unroll
         for (int i = 0; i < MI; ++i) {
             const int kr = i < 8 ? lane + 64 * i : P2;
             bad |= !(__builtin_fabsf(mra[i]) <= 0x1p20f) | !(__builtin_fabsf(mrb[i]) <= 0x1p20f);  // (NaN too)
             const float g = gl[kr];
             const float ga = g * mra[i], gb = g * mrb[i];
+            peak_a = __builtin_fmaxf(peak_a, __builtin_fabsf(ga));
+            peak_b = __builtin_fmaxf(peak_b, __builtin_fabsf(gb));
             if (i < 8 || lane == 0) cst[kr] = dev::pc_mk(0.5f * (ga + gb), 0.5f * (ga - gb));
         }
-        return __builtin_amdgcn_ballot_w64(bad) == 0;
+        return pair_code_paired(pair_code(bad, peak_a != 0.0f, peak_b != 0.0f), true);  // (row b past F is row a again)
     };
     // bin kb = pbl + 64 d: real bin kr = kb (d < 8), N - kb (d >= 8; d = 8, pbl = 0: 512 both ways)
     const dev::pc* const cb1 = cst + pbl;
@@ -229,7 +235,9 @@ __global__ __launch_bounds__(64 * kMW, CRLOT_PAIR_MASK_WAVES) void k_pair_mask(c
         load_hop(nxt + SH, (k + NB + 2) * H - a.pad);
         const bool more = k + 2 < f1;
         if (more) load_rows(k + 2);  // (in flight during this pair)
-        const bool paired = mok && (hopok & kPairHops) == kPairHops;
+        // (a lone all-zero input frame, as a lone gated one, is done alone: exact zeros; fused_common.h)
+        const bool paired = mok && (hopok & kPairHops) == kPairHops &&
+                            pair_code_paired(hops_live_code<NB>(hoplive), k + 1 < a.F);
         dev::pc v[E];
         if (paired) {
 #pragma unroll
@@ -305,6 +313,7 @@ __global__ __launch_bounds__(64 * kMW, CRLOT_PAIR_MASK_WAVES) void k_pair_mask(c
         }
         if (more) mok = stage_rows();
         hopok = (hopok | hop_ok<SH>(nxt, xlo, xhi) << (NB + 1) | hop_ok<SH>(nxt + SH, xlo, xhi) << (NB + 2)) >> 2;
+        hoplive = (hoplive | hop_live<SH>(nxt) << (NB + 1) | hop_live<SH>(nxt + SH) << (NB + 2)) >> 2;
 #pragma unroll
         for (int m = 0; m < E + SH - 2 * SH; ++m) xin[m] = xin[m + 2 * SH];
 #pragma unroll
@@ -398,11 +407,12 @@ __global__ __launch_bounds__(64 * kMW) void k_pair512_mask(const MaskWalkArgs ma
 #pragma unroll
         for (int qq = 0; qq < SH; ++qq) acc[NB - 1][qq] = 0.f;
     };
-    uint32_t hopok = 0;
+    uint32_t hopok = 0, hoplive = 0;  // (hoplive: the hop holds a non-zero sample, hop_live)
 #pragma unroll
     for (int h = 0; h <= NB; ++h) {
         load_hop(xin + h * SH, (fs + h) * H - a.pad);
         hopok |= hop_ok<SH>(xin + h * SH, xlo, xhi) << h;
+        hoplive |= hop_live<SH>(xin + h * SH) << h;
     }
 #pragma unroll
     for (int j = 0; j < NB; ++j)
@@ -426,15 +436,18 @@ __global__ __launch_bounds__(64 * kMW) void k_pair512_mask(const MaskWalkArgs ma
     };
     auto stage_rows = [&]() -> bool {
         bool bad = false;
+        float peak_a = 0.0f, peak_b = 0.0f;  // (max |g m| of frame a / b in this lane)
 #pragma unroll
         for (int i = 0; i < MI; ++i) {
             const int kr = i < 4 ? lane + 64 * i : P2;
             bad |= !(__builtin_fabsf(mra[i]) <= 0x1p20f) | !(__builtin_fabsf(mrb[i]) <= 0x1p20f);  // (NaN too)
             const float g = gain_at(kr);
             const float ga = g * mra[i], gb = g * mrb[i];
+            peak_a = __builtin_fmaxf(peak_a, __builtin_fabsf(ga));
+            peak_b = __builtin_fmaxf(peak_b, __builtin_fabsf(gb));
             if (i < 4 || lane == 0) cst[kr] = dev::pc_mk(0.5f * (ga + gb), 0.5f * (ga - gb));
         }
-        return __builtin_amdgcn_ballot_w64(bad) == 0;
+        return pair_code_paired(pair_code(bad, peak_a != 0.0f, peak_b != 0.0f), true);  // (row b past F is row a again)
     };
     const dev::pc* const cb1 = cst + q;
     const dev::pc* const cb2 = cst - q;
@@ -446,7 +459,9 @@ __global__ __launch_bounds__(64 * kMW) void k_pair512_mask(const MaskWalkArgs ma
         load_hop(nxt + SH, (k + NB + 2) * H - a.pad);
         const bool more = k + 2 < f1;
         if (more) load_rows(k + 2);
-        const bool paired = mok && (hopok & kPairHops) == kPairHops;
+        // (a lone all-zero input frame, as a lone gated one, is done alone: exact zeros; fused_common.h)
+        const bool paired = mok && (hopok & kPairHops) == kPairHops &&
+                            pair_code_paired(hops_live_code<NB>(hoplive), k + 1 < a.F);
         dev::pc v[E];
         if (paired) {
 #pragma unroll
@@ -505,6 +520,7 @@ __global__ __launch_bounds__(64 * kMW) void k_pair512_mask(const MaskWalkArgs ma
         }
         if (more) mok = stage_rows();
         hopok = (hopok | hop_ok<SH>(nxt, xlo, xhi) << (NB + 1) | hop_ok<SH>(nxt + SH, xlo, xhi) << (NB + 2)) >> 2;
+        hoplive = (hoplive | hop_live<SH>(nxt) << (NB + 1) | hop_live<SH>(nxt + SH) << (NB + 2)) >> 2;
 #pragma unroll
         for (int m = 0; m < E + SH - 2 * SH; ++m) xin[m] = xin[m + 2 * SH];
 #pragma unroll

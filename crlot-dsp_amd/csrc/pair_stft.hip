@@ -113,11 +113,12 @@ __global__ __launch_bounds__(64 * kSW, 3) void k_pair_stft(const PairSpecArgs pa
     auto load_hop = [&](float* dst, int origin) { load_hop1<SH>(dst, rx, lane, origin, a.T, a.pad_mode); };
 
     float xin[E + SH];  // hops k .. k+NB of the pair at k
-    uint32_t hopok = 0;
+    uint32_t hopok = 0, hoplive = 0;  // (hoplive: the hop holds a non-zero sample, hop_live)
 #pragma unroll
     for (int h = 0; h <= NB; ++h) {
         load_hop(xin + h * SH, (f0 + h) * H - a.pad);
         hopok |= hop_ok<SH>(xin + h * SH, xlo, xhi) << h;
+        hoplive |= hop_live<SH>(xin + h * SH) << h;
     }
     // bins k = pbl + 64 d <= N/2 of a frame: d < 8 in every lane, d = 8 in lane 0 (k = N/2)
     auto store_bins = [&](float* row, auto valfn) {
@@ -141,7 +142,8 @@ __global__ __launch_bounds__(64 * kSW, 3) void k_pair_stft(const PairSpecArgs pa
         float* ra = so + int64_t(k) * pa.ld_frame;
         float* rb = ra + pa.ld_frame;
         dev::pc v[E];
-        if ((hopok & kPairHops) == kPairHops) {
+        // (a lone all-zero frame of the pair is transformed alone: exact zeros; fused_common.h)
+        if ((hopok & kPairHops) == kPairHops && pair_code_paired(hops_live_code<NB>(hoplive), two)) {
 #pragma unroll
             for (int m4 = 0; m4 < E / 4; ++m4) {
                 const float4 w = *reinterpret_cast<const float4*>(wa4 + m4 * 256 + lane * 4);
@@ -187,6 +189,7 @@ __global__ __launch_bounds__(64 * kSW, 3) void k_pair_stft(const PairSpecArgs pa
             }
         }
         hopok = (hopok | hop_ok<SH>(nxt, xlo, xhi) << (NB + 1) | hop_ok<SH>(nxt + SH, xlo, xhi) << (NB + 2)) >> 2;
+        hoplive = (hoplive | hop_live<SH>(nxt) << (NB + 1) | hop_live<SH>(nxt + SH) << (NB + 2)) >> 2;
 #pragma unroll
         for (int m = 0; m < E + SH - 2 * SH; ++m) xin[m] = xin[m + 2 * SH];
 #pragma unroll
@@ -319,8 +322,9 @@ __global__ __launch_bounds__(64 * kSW, (PairIstftOcc<SH, MASK>::value)) void k_p
         }
     };
     // (A', B') of real bin kr at buf[kr] = A', buf[513 + kr] = B'; true when the pair keeps the paired regime
-    auto stage = [&]() -> bool {
+    auto stage = [&](bool has_b) -> bool {
         bool bad = false;
+        float peak_a = 0.0f, peak_b = 0.0f;  // (max |stepped value| of frame a / b in this lane; a NaN is `bad`)
 #pragma unroll
         for (int i = 0; i < MI; ++i) {
             const int kr = i < 8 ? lane + 64 * i : P2;
@@ -333,15 +337,18 @@ __global__ __launch_bounds__(64 * kSW, (PairIstftOcc<SH, MASK>::value)) void k_p
                 by *= mb_[i];
             }
             if (kr == 0 || kr == P2) ay = by = 0.0f;
-            const float m = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(ax), __builtin_fabsf(ay)),
-                                            __builtin_fmaxf(__builtin_fabsf(bx), __builtin_fabsf(by)));
+            const float m_a = __builtin_fmaxf(__builtin_fabsf(ax), __builtin_fabsf(ay));
+            const float m_b = __builtin_fmaxf(__builtin_fabsf(bx), __builtin_fabsf(by));
+            const float m = __builtin_fmaxf(m_a, m_b);
+            peak_a = __builtin_fmaxf(peak_a, m_a);
+            peak_b = __builtin_fmaxf(peak_b, m_b);
             bad |= !(m <= 0x1p60f) | (ax != ax) | (ay != ay) | (bx != bx) | (by != by);  // (NaN, Inf, huge)
             if (i < 8 || lane == 0) {
                 buf[kr] = dev::pc_mk(ax, ay);
                 buf[P2 + 1 + kr] = dev::pc_mk(bx, by);
             }
         }
-        return __builtin_amdgcn_ballot_w64(bad) == 0;
+        return pair_code_paired(pair_code(bad, peak_a != 0.0f, peak_b != 0.0f), has_b);  // (a lone all-zero member: per frame)
     };
     // bin kb = pbl + 64 d: real bin kb (d < 8) or N - kb (d >= 8, conjugated; d = 8 in
     // lane 0 is bin N/2 itself, whose imaginary part is zero either way)
@@ -349,7 +356,7 @@ __global__ __launch_bounds__(64 * kSW, (PairIstftOcc<SH, MASK>::value)) void k_p
     const dev::pc* const cb = buf - pbl;
     load_rows(fs);
     for (int k = fs; k < f1; k += 2) {
-        const bool paired = stage();
+        const bool paired = stage(k + 1 < a.F);
         dev::wave_lds_fence();
         const bool more = k + 2 < f1;
         dev::pc v[E];
@@ -377,7 +384,7 @@ __global__ __launch_bounds__(64 * kSW, (PairIstftOcc<SH, MASK>::value)) void k_p
             for (int p = 0; p < npass; ++p) {
                 if (p) {
                     dev::wave_lds_fence();
-                    (void)stage();
+                    (void)stage(true);
                     dev::wave_lds_fence();
                 }
 #pragma unroll
@@ -434,11 +441,12 @@ __global__ __launch_bounds__(64 * kSW) void k_pair512_stft(const PairSpecArgs pa
     for (int m = 0; m < E; ++m) wa[m] = a.t.wa[lane + 64 * m];
     auto load_hop = [&](float* dst, int origin) { load_hop1<SH>(dst, rx, lane, origin, a.T, a.pad_mode); };
     float xin[E + SH];
-    uint32_t hopok = 0;
+    uint32_t hopok = 0, hoplive = 0;  // (hoplive: the hop holds a non-zero sample, hop_live)
 #pragma unroll
     for (int h = 0; h <= NB; ++h) {
         load_hop(xin + h * SH, (f0 + h) * H - a.pad);
         hopok |= hop_ok<SH>(xin + h * SH, xlo, xhi) << h;
+        hoplive |= hop_live<SH>(xin + h * SH) << h;
     }
     auto store_bins = [&](float* row, auto valfn) {  // bins q + 64 d <= N/2: d < 4, and d = 4 in lane 0
         float2* r2 = reinterpret_cast<float2*>(row);
@@ -461,7 +469,8 @@ __global__ __launch_bounds__(64 * kSW) void k_pair512_stft(const PairSpecArgs pa
         float* ra = so + int64_t(k) * pa.ld_frame;
         float* rb = ra + pa.ld_frame;
         dev::pc v[E];
-        if ((hopok & kPairHops) == kPairHops) {
+        // (a lone all-zero frame of the pair is transformed alone: exact zeros; fused_common.h)
+        if ((hopok & kPairHops) == kPairHops && pair_code_paired(hops_live_code<NB>(hoplive), two)) {
 #pragma unroll
             for (int m = 0; m < E; ++m) v[m] = dev::pc_mk(xin[m] * wa[m], xin[m + SH] * wa[m]);
             dev::wave_lds_fence();
@@ -492,6 +501,7 @@ __global__ __launch_bounds__(64 * kSW) void k_pair512_stft(const PairSpecArgs pa
             }
         }
         hopok = (hopok | hop_ok<SH>(nxt, xlo, xhi) << (NB + 1) | hop_ok<SH>(nxt + SH, xlo, xhi) << (NB + 2)) >> 2;
+        hoplive = (hoplive | hop_live<SH>(nxt) << (NB + 1) | hop_live<SH>(nxt + SH) << (NB + 2)) >> 2;
 #pragma unroll
         for (int m = 0; m < E + SH - 2 * SH; ++m) xin[m] = xin[m + 2 * SH];
 #pragma unroll
@@ -591,8 +601,9 @@ __global__ __launch_bounds__(64 * kSW) void k_pair512_istft(const PairSpecArgs p
             }
         }
     };
-    auto stage = [&]() -> bool {
+    auto stage = [&](bool has_b) -> bool {
         bool bad = false;
+        float peak_a = 0.0f, peak_b = 0.0f;  // (max |stepped value| of frame a / b in this lane; a NaN is `bad`)
 #pragma unroll
         for (int i = 0; i < MI; ++i) {
             const int kr = i < 4 ? lane + 64 * i : P2;
@@ -605,21 +616,24 @@ __global__ __launch_bounds__(64 * kSW) void k_pair512_istft(const PairSpecArgs p
                 by *= mb_[i];
             }
             if (kr == 0 || kr == P2) ay = by = 0.0f;
-            const float m = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(ax), __builtin_fabsf(ay)),
-                                            __builtin_fmaxf(__builtin_fabsf(bx), __builtin_fabsf(by)));
+            const float m_a = __builtin_fmaxf(__builtin_fabsf(ax), __builtin_fabsf(ay));
+            const float m_b = __builtin_fmaxf(__builtin_fabsf(bx), __builtin_fabsf(by));
+            const float m = __builtin_fmaxf(m_a, m_b);
+            peak_a = __builtin_fmaxf(peak_a, m_a);
+            peak_b = __builtin_fmaxf(peak_b, m_b);
             bad |= !(m <= 0x1p60f) | (ax != ax) | (ay != ay) | (bx != bx) | (by != by);
             if (i < 4 || lane == 0) {
                 buf[kr] = dev::pc_mk(ax, ay);
                 buf[P2 + 1 + kr] = dev::pc_mk(bx, by);
             }
         }
-        return __builtin_amdgcn_ballot_w64(bad) == 0;
+        return pair_code_paired(pair_code(bad, peak_a != 0.0f, peak_b != 0.0f), has_b);
     };
     const dev::pc* const ca = buf + q;
     const dev::pc* const cb = buf - q;
     load_rows(fs);
     for (int k = fs; k < f1; k += 2) {
-        const bool paired = stage();
+        const bool paired = stage(k + 1 < a.F);
         dev::wave_lds_fence();
         const bool more = k + 2 < f1;
         dev::pc v[E];
@@ -647,7 +661,7 @@ __global__ __launch_bounds__(64 * kSW) void k_pair512_istft(const PairSpecArgs p
             for (int p = 0; p < npass; ++p) {
                 if (p) {
                     dev::wave_lds_fence();
-                    (void)stage();
+                    (void)stage(true);
                     dev::wave_lds_fence();
                 }
 #pragma unroll

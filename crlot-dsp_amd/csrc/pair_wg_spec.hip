@@ -203,6 +203,16 @@ struct WgSmem {
         for (int w = 0; w < G::L / 64; ++w) v &= votes[4 * set + w];
         return v != 0u;
     }
+    // the same for a pair code (pair_code, fused_common.h): posted per wave, ORed after the barrier
+    __device__ __forceinline__ void post_code(int wave, int lane, uint32_t code, int set = 0) {
+        if (lane == 0) votes[4 * set + wave] = code;
+    }
+    __device__ __forceinline__ uint32_t any_code(int set = 0) const {
+        uint32_t v = 0u;
+#pragma unroll
+        for (int w = 0; w < G::L / 64; ++w) v |= votes[4 * set + w];
+        return v;
+    }
 };
 
 // hop of H = L SH samples at `origin`, lane t holding samples origin + t + L q,
@@ -308,16 +318,22 @@ __global__ __launch_bounds__(G::L, 2) void k_pairwg_stft(const PairSpecArgs pa) 
     auto load_hop = [&](float* dst, int origin) { load_hop_wg<L, SH>(dst, rx, t, origin, a.T, a.pad_mode); };
 
     float xin[E + SH];  // hops k .. k+NB of the pair at k
-    uint32_t hopok = 0;
+    uint32_t hopok = 0, hoplive = 0;  // (hoplive: the hop holds a non-zero sample, hop_live)
 #pragma unroll
     for (int h = 0; h <= NB; ++h) {
         load_hop(xin + h * SH, (f0 + h) * H - a.pad);
         hopok |= hop_ok<SH>(xin + h * SH, xlo, xhi) << h;
+        hoplive |= hop_live<SH>(xin + h * SH) << h;
     }
     constexpr uint32_t kPairHops = (1u << (NB + 1)) - 1;
-    sm.post(wave, lane, (hopok & kPairHops) == kPairHops);
+    // this wave's pair code of the hops: a sample outside the paired range; frame a / b holds a
+    // non-zero sample (a lone all-zero frame is transformed alone: exact zeros; fused_common.h)
+    auto hops_code = [&]() {
+        return ((hopok & kPairHops) == kPairHops ? 0u : kPairBad) | hops_live_code<NB>(hoplive);
+    };
+    sm.post_code(wave, lane, hops_code());
     __syncthreads();
-    bool paired = sm.all();
+    bool paired = pair_code_paired(sm.any_code(), f0 + 1 < a.F);
     for (int k = f0; k < f1; k += 2) {
         float nxt[2 * SH];
         load_hop(nxt, (k + NB + 1) * H - a.pad);
@@ -358,9 +374,10 @@ __global__ __launch_bounds__(G::L, 2) void k_pairwg_stft(const PairSpecArgs pa) 
         // the next pair's regime; the barrier also keeps the staged reads ahead of
         // the next exchange's writes
         hopok = (hopok | hop_ok<SH>(nxt, xlo, xhi) << (NB + 1) | hop_ok<SH>(nxt + SH, xlo, xhi) << (NB + 2)) >> 2;
-        sm.post(wave, lane, (hopok & kPairHops) == kPairHops);
+        hoplive = (hoplive | hop_live<SH>(nxt) << (NB + 1) | hop_live<SH>(nxt + SH) << (NB + 2)) >> 2;
+        sm.post_code(wave, lane, hops_code());
         __syncthreads();
-        paired = sm.all();
+        paired = pair_code_paired(sm.any_code(), k + 3 < a.F);
 #pragma unroll
         for (int m = 0; m < E + SH - 2 * SH; ++m) xin[m] = xin[m + 2 * SH];
 #pragma unroll
@@ -424,9 +441,11 @@ __global__ __launch_bounds__(G::L, 2) void k_pairwg_istft(const PairSpecArgs pa)
             }
         }
     };
-    // (A', B') of real bin kr at xb[spad(kr)], xb[OB + spad(kr)]; true when this lane keeps the paired regime
-    auto stage = [&]() -> bool {
+    // (A', B') of real bin kr at xb[spad(kr)], xb[OB + spad(kr)]; returns the wave's pair code
+    // (a lone all-zero member is done alone: pair_code, fused_common.h)
+    auto stage = [&]() -> uint32_t {
         bool bad = false;
+        float peak_a = 0.0f, peak_b = 0.0f;  // (max |stepped value| of frame a / b in this lane; a NaN is `bad`)
 #pragma unroll
         for (int i = 0; i <= NI; ++i) {
             const int kr = i < NI ? t + L * i : P2;
@@ -440,21 +459,24 @@ __global__ __launch_bounds__(G::L, 2) void k_pairwg_istft(const PairSpecArgs pa)
                 by *= mb_[i];
             }
             if (kr == 0 || kr == P2) ay = by = 0.0f;
-            const float m = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(ax), __builtin_fabsf(ay)),
-                                            __builtin_fmaxf(__builtin_fabsf(bx), __builtin_fabsf(by)));
+            const float m_a = __builtin_fmaxf(__builtin_fabsf(ax), __builtin_fabsf(ay));
+            const float m_b = __builtin_fmaxf(__builtin_fabsf(bx), __builtin_fabsf(by));
+            const float m = __builtin_fmaxf(m_a, m_b);
             bad |= !(m <= 0x1p60f) | (ax != ax) | (ay != ay) | (bx != bx) | (by != by);  // (NaN, Inf, huge)
+            peak_a = __builtin_fmaxf(peak_a, m_a);  // (lanes that are not `on` hold zeros)
+            peak_b = __builtin_fmaxf(peak_b, m_b);
             if (on) {
                 sm.xb[spad(kr)] = dev::pc_mk(ax, ay);
                 sm.xb[OB + spad(kr)] = dev::pc_mk(bx, by);
             }
         }
-        return !bad;
+        return pair_code(bad, peak_a != 0.0f, peak_b != 0.0f);
     };
     for (int k = fs; k < f1; k += 2) {
         load_rows(k);
-        sm.post(wave, lane, __builtin_amdgcn_ballot_w64(!stage()) == 0);
+        sm.post_code(wave, lane, stage());
         __syncthreads();
-        const bool paired = sm.all();
+        const bool paired = pair_code_paired(sm.any_code(), k + 1 < a.F);
         dev::pc v[E];
         if (paired) {
 #pragma unroll
@@ -541,39 +563,39 @@ __global__ __launch_bounds__(G::L, 2) void k_pairwg_mask(const PairSpecArgs pa) 
         for (int i = 0; i <= NI; ++i) {
             const int kr = i < NI ? t + L * i : P2;
             const bool on = i < NI || t == 0;
-            ma_[i] = on ? r0[kr] : 1.0f;
-            mb_[i] = on ? r1[kr] : 1.0f;
+            ma_[i] = on ? r0[kr] : 0.0f;  // (the others: unused by the step, silent in its verdict)
+            mb_[i] = on ? r1[kr] : 0.0f;
         }
-    };
-    auto rows_ok = [&]() {
-        bool bad = false;
-#pragma unroll
-        for (int i = 0; i <= NI; ++i)
-            bad |= !(__builtin_fabsf(ma_[i]) <= 0x1p20f) | !(__builtin_fabsf(mb_[i]) <= 0x1p20f);  // (NaN too)
-        return __builtin_amdgcn_ballot_w64(bad) == 0;
     };
 
     float xin[E + SH];
-    uint32_t hopok = 0;
+    uint32_t hopok = 0, hoplive = 0;  // (hoplive: the hop holds a non-zero sample, hop_live)
 #pragma unroll
     for (int h = 0; h <= NB; ++h) {
         load_hop(xin + h * SH, (fs + h) * H - a.pad);
         hopok |= hop_ok<SH>(xin + h * SH, xlo, xhi) << h;
+        hoplive |= hop_live<SH>(xin + h * SH) << h;
     }
     constexpr uint32_t kPairHops = (1u << (NB + 1)) - 1;
     // verdict set 0: the pair's hops (posted one pair ahead); set 1: its mask rows
     // (loaded after the forward, so they are live across no transform, and
     // checked at the step: a row that leaves the paired regime drops the pair's
     // paired forward and the pair is done frame by frame)
-    sm.post(wave, lane, (hopok & kPairHops) == kPairHops);
+    // this wave's pair code of the hops: a sample outside the paired range; frame a / b holds a
+    // non-zero sample (a lone all-zero input frame is done alone: exact zeros; fused_common.h)
+    auto hops_code = [&]() {
+        return ((hopok & kPairHops) == kPairHops ? 0u : kPairBad) | hops_live_code<NB>(hoplive);
+    };
+    sm.post_code(wave, lane, hops_code());
     __syncthreads();
-    bool hops_paired = sm.all();
+    bool hops_paired = pair_code_paired(sm.any_code(), fs + 1 < a.F);
     for (int k = fs; k < f1; k += 2) {
         float nxt[2 * SH];
         load_hop(nxt, (k + NB + 1) * H - a.pad);
         load_hop(nxt + SH, (k + NB + 2) * H - a.pad);
         hopok = (hopok | hop_ok<SH>(nxt, xlo, xhi) << (NB + 1) | hop_ok<SH>(nxt + SH, xlo, xhi) << (NB + 2)) >> 2;
-        const bool next_hops = (hopok & kPairHops) == kPairHops;
+        hoplive = (hoplive | hop_live<SH>(nxt) << (NB + 1) | hop_live<SH>(nxt + SH) << (NB + 2)) >> 2;
+        const uint32_t next_hops = hops_code();
         dev::pc v[E];
         bool done = false;
         if (hops_paired) {
@@ -588,15 +610,21 @@ __global__ __launch_bounds__(G::L, 2) void k_pairwg_mask(const PairSpecArgs pa) 
             for (int d = 0; d < E; ++d) sm.xb[spad(G::bin(t, d))] = v[d];
             load_rows(k);
             __syncthreads();
-            sm.post(wave, lane, rows_ok(), 1);
-            // the step on this lane's bin pairs {kr, N - kr}, in place
+            // the step on this lane's bin pairs {kr, N - kr}, in place, and the rows' verdict:
+            // a value outside the paired regime, or a lone member whose multipliers g m are
+            // all zero (a gated frame next to an open one is done alone: pair_code, fused_common.h)
+            bool bad = false;
+            float peak_a = 0.0f, peak_b = 0.0f;  // (max |g m| of frame a / b in this lane)
 #pragma unroll
             for (int i = 0; i <= NI; ++i) {
                 const int kr = i < NI ? t + L * i : P2;
-                const bool on = i < NI || t == 0;
+                const bool on = i < NI || t == 0;  // (the others hold zeros)
                 const int jr = (N - kr) & (N - 1);
                 const float g = a.t.gain ? a.t.gain[kr] : 1.0f;
                 const float ga = g * ma_[i], gb = g * mb_[i];
+                bad |= !(__builtin_fabsf(ma_[i]) <= 0x1p20f) | !(__builtin_fabsf(mb_[i]) <= 0x1p20f);  // (NaN too)
+                peak_a = __builtin_fmaxf(peak_a, __builtin_fabsf(ga));
+                peak_b = __builtin_fmaxf(peak_b, __builtin_fabsf(gb));
                 const float c1 = 0.5f * (ga + gb), c2 = 0.5f * (ga - gb);
                 const dev::pc z = sm.xb[spad(kr)], zp = sm.xb[spad(jr)];
                 if (on) sm.xb[spad(kr)] = dev::pc_mk(__builtin_fmaf(c2, zp.x, c1 * z.x), __builtin_fmaf(-c2, zp.y, c1 * z.y));
@@ -604,13 +632,15 @@ __global__ __launch_bounds__(G::L, 2) void k_pairwg_mask(const PairSpecArgs pa) 
                     sm.xb[spad(jr)] =
                         dev::pc_mk(__builtin_fmaf(c2, z.x, c1 * zp.x), __builtin_fmaf(-c2, z.y, c1 * zp.y));
             }
+            sm.post_code(wave, lane, pair_code(bad, peak_a != 0.0f, peak_b != 0.0f), 1);
             __syncthreads();
-            if (sm.all(1)) {  // (uniform: otherwise no wave reads xb again before the frame-by-frame pass)
+            // (uniform: otherwise no wave reads xb again before the frame-by-frame pass; row b past F is row a again)
+            if (pair_code_paired(sm.any_code(1), true)) {
 #pragma unroll
                 for (int d = 0; d < E; ++d) v[d] = sm.xb[spad(G::bin(t, d))];
                 // the next pair's hop verdict; the barrier also keeps these reads ahead
                 // of the inverse's exchange writes
-                sm.post(wave, lane, next_hops);
+                sm.post_code(wave, lane, next_hops);
                 __syncthreads();
                 tw.inv(v, sm.xb, sm.tb, t);
                 float dr0[2 * SH], dr1[2 * SH];
@@ -654,10 +684,10 @@ __global__ __launch_bounds__(G::L, 2) void k_pairwg_mask(const PairSpecArgs pa) 
             };
             pass(std::integral_constant<int, 0>());
             if (k + 1 < f1) pass(std::integral_constant<int, 1>());
-            sm.post(wave, lane, next_hops);
+            sm.post_code(wave, lane, next_hops);
             __syncthreads();
         }
-        hops_paired = sm.all();
+        hops_paired = pair_code_paired(sm.any_code(), k + 3 < a.F);
 #pragma unroll
         for (int m = 0; m < E + SH - 2 * SH; ++m) xin[m] = xin[m + 2 * SH];
 #pragma unroll

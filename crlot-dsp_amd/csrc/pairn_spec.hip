@@ -98,6 +98,19 @@ struct QNSmem {
             return r;
         }
     }
+    // the walk's pair code (pair_code, fused_common.h): the wave's, or both waves' ORed
+    __device__ __forceinline__ uint32_t any(uint32_t wave_code) const {
+        if constexpr (QN<K>::L == 64) {
+            return wave_code;
+        } else {
+            const int wave = threadIdx.x >> 6;
+            if ((threadIdx.x & 63) == 0) votes[wave] = wave_code;
+            __syncthreads();
+            const uint32_t r = votes[0] | votes[1];
+            __syncthreads();  // (both read before the next post)
+            return r;
+        }
+    }
 };
 // the plan's pass twiddles into LDS (the whole workgroup), then a barrier
 template <int K>
@@ -131,6 +144,14 @@ __device__ __forceinline__ bool qn_ok(const float (&f)[E], float lo, float hi) {
         bad |= !((a >= lo) & (a <= hi)) & (a != 0.0f);
     }
     return __builtin_amdgcn_ballot_w64(bad) == 0;
+}
+
+// the wave's pair code of a pair's input frames: a sample outside the paired range;
+// frame a / b holds a non-zero sample (a lone all-zero frame is transformed alone:
+// exact zeros; pair_code, fused_common.h)
+template <int E>
+__device__ __forceinline__ uint32_t qn_frames_code(const float (&fa)[E], const float (&fb)[E], float lo, float hi) {
+    return pair_code(!(qn_ok(fa, lo, hi) && qn_ok(fb, lo, hi)), any_nonzero<E>(fa), any_nonzero<E>(fb));
 }
 
 // The per-walk OLA ring over the natural-order inverse output in the buffer:
@@ -232,7 +253,7 @@ __global__ __launch_bounds__(QN<K>::THREADS, 2) void k_pn_stft(const PairSpecArg
         const bool two = k + 1 < f1;
         float2* ra = reinterpret_cast<float2*>(so + int64_t(k) * pa.ld_frame);
         float2* rb = reinterpret_cast<float2*>(so + int64_t(k + 1) * pa.ld_frame);
-        const bool paired = sm.all(qn_ok(fa, xlo, xhi) && qn_ok(fb, xlo, xhi));
+        const bool paired = pair_code_paired(sm.any(qn_frames_code(fa, fb, xlo, xhi)), two);
         auto pass = [&](auto pc_) {  // P = 0 / 1: frame k / k+1 alone; paired: both (P = 0)
             constexpr int P = decltype(pc_)::value;
 #pragma unroll
@@ -289,13 +310,15 @@ __global__ __launch_bounds__(QN<K>::THREADS, 2) void k_pn_istft(const PairSpecAr
     // the pair's rows (and mask rows) by real bin kr = t + L i <= N/2, coalesced;
     // stepped -- (X g) m, re and im each; DC and Nyquist imaginary parts dropped
     float2 ra_[IB], rb_[IB];
-    auto load_rows = [&](int k) -> bool {
+    // -> the wave's pair code (a lone all-zero member is done alone: pair_code, fused_common.h)
+    auto load_rows = [&](int k) -> uint32_t {
         const float2* ra = reinterpret_cast<const float2*>(sb + int64_t(k) * pa.ld_frame);
         const float2* rb = reinterpret_cast<const float2*>(sb + int64_t(k + 1) * pa.ld_frame);
         const bool two = k + 1 < a.F;
         const float* m0 = MASK ? mrow0 + int64_t(k) * pa.mask.ld_frame : nullptr;
         const float* m1 = MASK && two ? m0 + pa.mask.ld_frame : m0;
         bool bad = false;
+        float peak_a = 0.0f, peak_b = 0.0f;  // (this lane's max |value| of frame a / b; a NaN is `bad`)
 #pragma unroll
         for (int i = 0; i < IB; ++i) {
             const int kr = t + G::L * i;
@@ -312,13 +335,16 @@ __global__ __launch_bounds__(QN<K>::THREADS, 2) void k_pn_istft(const PairSpecAr
                 by *= mb;
             }
             if (kr == 0 || kr == P2) ay = by = 0.0f;
-            const float mx = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(ax), __builtin_fabsf(ay)),
-                                             __builtin_fmaxf(__builtin_fabsf(bx), __builtin_fabsf(by)));
+            const float m_a = __builtin_fmaxf(__builtin_fabsf(ax), __builtin_fabsf(ay));
+            const float m_b = __builtin_fmaxf(__builtin_fabsf(bx), __builtin_fabsf(by));
+            const float mx = __builtin_fmaxf(m_a, m_b);
+            peak_a = __builtin_fmaxf(peak_a, m_a);
+            peak_b = __builtin_fmaxf(peak_b, m_b);
             bad |= !(mx <= 0x1p60f) | (ax != ax) | (ay != ay) | (bx != bx) | (by != by);  // (NaN, Inf, huge)
             ra_[i] = make_float2(ax, ay);
             rb_[i] = make_float2(bx, by);
         }
-        return __builtin_amdgcn_ballot_w64(bad) == 0;
+        return pair_code(bad, peak_a != 0.0f, peak_b != 0.0f);
     };
     // the full spectrum in natural order: the pair form Z = A' + i B' (conjugate-
     // extended above N/2), or frame p's own X (Hermitian)
@@ -344,7 +370,7 @@ __global__ __launch_bounds__(QN<K>::THREADS, 2) void k_pn_istft(const PairSpecAr
         dev::pn_fence<K>();
     };
     for (int k = w.fs; k < w.f1; k += 2) {
-        if (sm.all(load_rows(k))) {
+        if (pair_code_paired(sm.any(load_rows(k)), k + 1 < a.F)) {
             put(0);
             G::inv(sm.buf, sm.tw, t);
             ola.template push<false>(sm.buf, wsg, a.inv_n, k);
@@ -393,23 +419,31 @@ __global__ __launch_bounds__(QN<K>::THREADS, 2) void k_pn_mask(const PairSpecArg
     const float* mrow0 = pa.mask.p + int64_t(w.s) * pa.mask.ld_stream;
     auto row_a = [&](int k) { return mrow0 + int64_t(k) * pa.mask.ld_frame; };
     auto row_b = [&](int k) { return k + 1 < a.F ? row_a(k) + pa.mask.ld_frame : row_a(k); };  // (past F: unused)
-    float ma[IB], mb[IB];  // the pair's mask rows by real bin t + L i (<= N/2; 1 beyond)
+    float ma[IB], mb[IB];  // the pair's mask rows by real bin t + L i (<= N/2; 0 beyond: unused by the step, silent in its verdict)
     auto load_rows = [&](int k) {
         const float* r0 = row_a(k);
         const float* r1 = row_b(k);
 #pragma unroll
         for (int i = 0; i < IB; ++i) {
             const int kr = t + G::L * i;
-            ma[i] = kr <= P2 ? r0[kr] : 1.0f;
-            mb[i] = kr <= P2 ? r1[kr] : 1.0f;
+            ma[i] = kr <= P2 ? r0[kr] : 0.0f;
+            mb[i] = kr <= P2 ? r1[kr] : 0.0f;
         }
     };
-    auto rows_ok = [&]() {
+    // the wave's pair code of the rows: a value outside the paired regime; frame a / b has a
+    // non-zero multiplier g m (a lone gated frame is done alone: pair_code, fused_common.h)
+    auto rows_code = [&]() -> uint32_t {
         bool bad = false;
+        float peak_a = 0.0f, peak_b = 0.0f;  // (this lane's max |value| of frame a / b; a NaN is `bad`)
 #pragma unroll
-        for (int i = 0; i < IB; ++i)
+        for (int i = 0; i < IB; ++i) {
+            const int kr = t + G::L * i;
             bad |= !(__builtin_fabsf(ma[i]) <= 0x1p20f) | !(__builtin_fabsf(mb[i]) <= 0x1p20f);  // (NaN too)
-        return __builtin_amdgcn_ballot_w64(bad) == 0;
+            const float g = kr <= P2 && a.t.gain ? a.t.gain[kr] : 1.0f;
+            peak_a = __builtin_fmaxf(peak_a, __builtin_fabsf(g * ma[i]));  // (beyond N/2: zeros)
+            peak_b = __builtin_fmaxf(peak_b, __builtin_fabsf(g * mb[i]));
+        }
+        return pair_code(bad, peak_a != 0.0f, peak_b != 0.0f);
     };
     float fa[E], fb[E];
     auto load = [&](float (&f)[E], int k) { qn_load<K>(f, rx, t, k * H - a.pad, a.T, a.pad_mode); };
@@ -417,8 +451,10 @@ __global__ __launch_bounds__(QN<K>::THREADS, 2) void k_pn_mask(const PairSpecArg
     load(fb, w.fs + 1);
     load_rows(w.fs);
     for (int k = w.fs; k < w.f1; k += 2) {
-        const bool paired = sm.all(qn_ok(fa, xlo, xhi) && qn_ok(fb, xlo, xhi) && rows_ok());
+        // the rows' code and the input frames' (frame b past F: no member; row b past F is row a again)
         const bool partner_frame = k + 1 < a.F;  // frame k+1 past the last: imaginary part 0
+        const uint32_t codes = sm.any(rows_code() | qn_frames_code(fa, fb, xlo, xhi) << 4);  // (one exchange for both)
+        const bool paired = pair_code_paired(codes & 15u, true) && pair_code_paired(codes >> 4, partner_frame);
         if (paired) {
 #pragma unroll
             for (int m = 0; m < E; ++m)

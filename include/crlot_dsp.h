@@ -309,17 +309,38 @@ int crlot_ola_gather(crlot_plan* plan, const float* d_frames, float* d_y, int32_
  * :83-122): spectrum k of stream s, N/2+1 complex bins as float pairs, at
  * d_spec[s*ld_spec + k*ld_frame + 2*b], b <= N/2.  ld_frame >= N+2 floats;
  * d_spec 8-byte aligned, ld_frame and ld_spec even.  F = crlot_frame_count(T)
- * frames per stream.  Bit-identical to crlot_rfft_batched on the windowed
- * frames.
+ * frames per stream.  With frame pairing 0: bit-identical to
+ * crlot_rfft_batched on the windowed frames.
  *
  * crlot_istft_ola: the synthesis half.  Spectra in that layout (F frames per
  * stream) -> the plan's spectral step (the per-bin gain of
  * crlot_plan_set_spectral_gain, then row k of the mask below) ->
  * IFftPlan::inverse (kiss_fftri, *1/N, sanitize; kissfft_adapter.cc:124-168)
  * -> push_frame_AoS(k*H) with the synthesis window and gain -> produce(H)
- * (OLAAccumulator.cc:124-221): d_y[s*ld_y + n], n < F*H.  Bit-identical to
- * crlot_irfft_batched of the stepped spectra + crlot_ola_gather.  The imaginary
- * parts of bins 0 and N/2 are ignored, as kiss_fftri ignores them.
+ * (OLAAccumulator.cc:124-221): d_y[s*ld_y + n], n < F*H.  With frame pairing 0:
+ * bit-identical to crlot_irfft_batched of the stepped spectra +
+ * crlot_ola_gather.  The imaginary parts of bins 0 and N/2 are ignored, as
+ * kiss_fftri ignores them.
+ *
+ * With frame pairing on (the default) these entries and the masked
+ * crlot_roundtrip run frames (2j, 2j+1) through one complex transform where the
+ * pair kernels exist, and the bit identities above become float32 tolerances:
+ *   - results are within float32 rounding of the per-frame formulation
+ *     (per stream rel-L2 1e-6, max-abs 4e-6 max|x|);
+ *   - block by block, the error of output block b is at most 4e-6 times the
+ *     largest inverse-transform output among the frames that overlap it AND
+ *     their pair mates (k ^ 1): a quiet frame may carry rounding noise of its
+ *     loud mate, never of a frame further away;
+ *   - a gated frame stays silent: a frame whose stepped spectrum (istft_ola) or
+ *     whose multiplier row gain * mask (masked round trip) is all zero is
+ *     inverted alone when its mate is not, so an output block all of whose
+ *     frames are gated is exactly +0, as with pairing 0;
+ *   - likewise a frame of exact zeros in x next to a live one is transformed
+ *     alone by crlot_stft and the masked crlot_roundtrip (its spectrum is exact
+ *     zeros, whatever mask attenuates its mate);
+ *   - the unmasked crlot_roundtrip (the hot pair walkers) keeps no such
+ *     exception: exact silence in x before an onset may carry up to 4e-6 times
+ *     the onset frame's scale for one hop.
  *
  * crlot_plan_set_spectral_mask: a time-varying spectral step.  Row (s, k) of
  * N/2+1 real floats at d_mask[s*ld_stream + k*ld_frame] multiplies frame k of
@@ -327,7 +348,9 @@ int crlot_ola_gather(crlot_plan* plan, const float* d_frames, float* d_y, int32_
  * every stream).  Device memory owned by the caller, read by every later
  * crlot_roundtrip, crlot_roundtrip_interleaved (stream = channel plane
  * g*C + c) and crlot_istft_ola on the plan until it is replaced or cleared
- * (NULL); it must hold a row for every frame those calls run.  With a mask,
+ * (NULL); it must hold a row for every frame those calls run (nothing here
+ * checks its extent: the Python binding does, before the call).  With a mask
+ * and frame pairing 0,
  * crlot_roundtrip(x) equals crlot_istft_ola(crlot_stft(x)) bit for bit (one
  * walk over HBM where the shape allows it: power-of-two N, H % 128 == 0,
  * N % H == 0, 8-byte aligned output rows).  The per-hop streaming object takes
