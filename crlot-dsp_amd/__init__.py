@@ -32,6 +32,11 @@ PAD_CONSTANT, PAD_REFLECT, PAD_EDGE = 0, 1, 2
 # dsp::fft::FftDomain
 FFT_REAL, FFT_COMPLEX = 0, 1
 
+# spectrogram features (crlot_features_desc) and the mel scales
+FEAT_POWER, FEAT_MAGNITUDE = 0, 1
+FEAT_LIN, FEAT_LN, FEAT_LOG10, FEAT_DB = 0, 1, 2, 3
+MEL_HTK, MEL_SLANEY = 0, 1
+
 OK, EINVAL, EUNSUPPORTED, EHIP, ENOMEM, ERUNTIME, ERANGE = 0, -1, -2, -3, -4, -5, -6
 
 
@@ -78,6 +83,11 @@ class OlaConfigC(C.Structure):
         ("shadow_ring", C.c_int32),
         ("device", C.c_int32),
     ]
+
+
+class FeaturesDesc(C.Structure):
+    """crlot_features_desc (include/crlot_dsp.h)."""
+    _fields_ = [("kind", C.c_int32), ("n_bands", C.c_int32), ("log", C.c_int32), ("floor", C.c_float)]
 
 
 class FftDesc(C.Structure):
@@ -137,6 +147,12 @@ def lib():
         "crlot_plan_set_spectral_mask": ([vp, vp, i64, i64], C.c_int),
         "crlot_stft": ([vp, vp, vp, i32, i64, i64, i64, i64, vp], C.c_int),
         "crlot_istft_ola": ([vp, vp, vp, i32, i64, i64, i64, i64, vp], C.c_int),
+        "crlot_features_create": ([vp, C.POINTER(FeaturesDesc), vp, C.POINTER(vp)], C.c_int),
+        "crlot_features_destroy": ([vp], None),
+        "crlot_features_info": ([vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)], C.c_int),
+        "crlot_spectrogram": ([vp, vp, vp, i32, i64, i64, i64, i64, vp], C.c_int),
+        "crlot_mel_filterbank": ([i32, i32, C.c_double, C.c_double, C.c_double, i32, i32, fp], C.c_int),
+        "crlot_filterbank_spans": ([fp, i32, i32, C.POINTER(i32), C.POINTER(i32)], C.c_int),
         "crlot_fft_plan_create": ([C.POINTER(FftDesc), C.POINTER(vp)], C.c_int),
         "crlot_fft_plan_destroy": ([vp], None),
         "crlot_fft_plan_info": ([vp, C.POINTER(i32), C.POINTER(i32)], C.c_int),
@@ -664,6 +680,119 @@ class Plan:
         _check(lib().crlot_irfft_batched(self._h, X.data_ptr(), out.data_ptr(), B, 2 * bins,
                                          1, n, 1, _stream_handle(X)),
                "crlot_irfft_batched")
+        return out
+
+
+def mel_filterbank(n_mels: int, nfft: int, sample_rate: float, fmin: float = 0.0, fmax: float | None = None,
+                   scale: int = MEL_HTK, slaney_norm: bool = False) -> np.ndarray:
+    """(n_mels, nfft/2+1) float32 triangular mel weights (crlot_mel_filterbank):
+    computed in double, rounded once; fmax None: sample_rate / 2."""
+    out = np.zeros((max(int(n_mels), 1), max(int(nfft), 0) // 2 + 1), np.float32)
+    _check(lib().crlot_mel_filterbank(int(n_mels), int(nfft), float(sample_rate), float(fmin),
+                                      0.0 if fmax is None else float(fmax), int(scale), int(bool(slaney_norm)),
+                                      _fptr(out)), "crlot_mel_filterbank")
+    return out
+
+
+def filterbank_spans(weights) -> tuple[np.ndarray, np.ndarray]:
+    """(lo, hi) of every row of a (n_bands, bins) filterbank: the first to one past
+    the last non-zero weight, (0, 0) for an all-zero row (crlot_filterbank_spans)."""
+    w = np.ascontiguousarray(weights, np.float32)
+    if w.ndim != 2 or w.shape[1] < 1:
+        raise ValueError("weights must be (n_bands, bins)")
+    lo, hi = np.zeros(w.shape[0], np.int32), np.zeros(w.shape[0], np.int32)
+    i32p = C.POINTER(C.c_int32)
+    _check(lib().crlot_filterbank_spans(_fptr(w), w.shape[0], w.shape[1], lo.ctypes.data_as(i32p),
+                                        hi.ctypes.data_as(i32p)), "crlot_filterbank_spans")
+    return lo, hi
+
+
+def _spectrogram_x_layout(shape, strides, dtype: str, device_index):
+    """Validate Features.spectrogram's input from its plain description (shape and
+    strides in elements as tuples, dtype name, device index or None for a host
+    tensor), as Plan.stft validates its own x.  Returns (S, T)."""
+    if len(shape) != 2 or len(strides) != 2:
+        raise ValueError("x must be (S, T) or (T,)")
+    if dtype != "float32":
+        raise ValueError(f"x must be float32, not {dtype}")
+    if device_index is None:
+        raise ValueError("x must be a device tensor")
+    if int(shape[1]) > 1 and int(strides[1]) != 1:
+        raise ValueError("x must have contiguous rows")
+    return int(shape[0]), int(shape[1])
+
+
+def _spectrogram_out_layout(shape, strides, dtype: str, device_index, S: int, F: int, n_out: int):
+    """The same for a caller's output tensor: (S, F, n_out) float32 on the device,
+    rows contiguous and at least n_out apart.  Returns (ld_out, ld_frame)."""
+    if dtype != "float32" or device_index is None:
+        raise ValueError("out must be a float32 device tensor")
+    if tuple(int(v) for v in shape) != (S, F, n_out) or len(strides) != 3:
+        raise ValueError(f"out must be ({S}, {F}, {n_out})")
+    if n_out > 1 and int(strides[2]) != 1:
+        raise ValueError("out must have contiguous rows")
+    # a size-1 dim's stride is meaningless: the dense value there
+    ld_frame = int(strides[1]) if F > 1 else n_out
+    ld_out = int(strides[0]) if S > 1 else F * n_out
+    if ld_frame < n_out or ld_out < 0:
+        raise ValueError("out rows overlap: ld_frame < n_out")
+    return ld_out, ld_frame
+
+
+def _tensor_layout(t):
+    return (tuple(t.shape), tuple(t.stride()), str(t.dtype).replace("torch.", ""),
+            (t.device.index if t.device.index is not None else 0) if t.is_cuda else None)
+
+
+class Features:
+    """Spectrogram features of a plan's STFT, computed where the spectrum would be
+    stored (crlot_features_create / crlot_spectrogram): per bin |X|^2 or |X|
+    (weights None), or the rows of a (n_bands, N/2+1) filterbank applied to them,
+    optionally logged (log FEAT_LN / FEAT_LOG10 / FEAT_DB of max(value, floor)).
+    Keeps a reference to the plan, which must outlive it."""
+
+    def __init__(self, plan: Plan, kind: int = FEAT_POWER, weights=None, log: int = FEAT_LIN, floor: float = 0.0):
+        self._h = None
+        bins = plan.frame_size // 2 + 1
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, np.float32)
+            if w.ndim != 2 or w.shape[1] != bins or w.shape[0] < 1:
+                raise ValueError("weights must be (n_bands, N/2+1)")
+        d = FeaturesDesc(int(kind), 0 if w is None else w.shape[0], int(log), float(floor))
+        h = C.c_void_p()
+        _check(lib().crlot_features_create(plan._h, C.byref(d), None if w is None else w.ctypes.data, C.byref(h)),
+               "crlot_features_create")
+        self._h, self.plan = h, plan
+        n_out, k, lg, widest = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        _check(lib().crlot_features_info(self._h, C.byref(n_out), C.byref(k), C.byref(lg), C.byref(widest)))
+        self.n_out, self.kind, self.log, self.widest_band = n_out.value, k.value, lg.value, widest.value
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().crlot_features_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # interpreter shutdown
+            pass
+
+    def spectrogram(self, x, out=None, stream: int | None = None):
+        """x: (S, T) or (T,) float32 device tensor -> (S, F, n_out) float32: frame k of
+        stream s framed, windowed and transformed exactly as Plan.stft, then the
+        feature (crlot_spectrogram)."""
+        if x.dim() == 1:
+            return self.spectrogram(x[None], None if out is None else out[None], stream)[0]
+        S, T = _spectrogram_x_layout(*_tensor_layout(x))
+        F = self.plan.frame_count(T)
+        if out is None:
+            out = _torch().empty((S, F, self.n_out), dtype=x.dtype, device=x.device)
+        ld_out, ld_frame = _spectrogram_out_layout(*_tensor_layout(out), S, F, self.n_out)
+        s = _stream_handle(x) if stream is None else stream
+        _check(lib().crlot_spectrogram(self._h, x.data_ptr(), out.data_ptr(), S, T, _ld(x, 0, T), ld_out, ld_frame,
+                                       s), "crlot_spectrogram")
         return out
 
 

@@ -1039,33 +1039,43 @@ int crlot_irfft_batched(crlot_plan* p, const float* d_in, float* d_out, int32_t 
 // crlot_istft_ola(crlot_stft(x)) bit for bit.
 namespace {
 
+// Which kernels crlot_stft runs for this plan and input (crlot_spectrogram follows
+// the same choice, so its spectrum is crlot_stft's bit for bit).
+enum class StftRoute { kPair, kPair15, kPairN, kWalk, kStaged };
+StftRoute stft_route(const crlot_plan* p, const crlot::DevTables& t, const float* d_x, int64_t T, int64_t ld_x) {
+    const int64_t lim = int64_t(1) << 29;
+    if (p->pairing && crlot::pair_spec_supported(p->geo.n, p->geo.h) && crlot::pair_tables(p->geo, t) && aligned4(d_x) && T < lim)
+        return StftRoute::kPair;  // N = 512 - 4096 frame pairs (pairing off: K_stft, bit-identical to crlot_rfft_batched)
+    if (p->pairing && crlot::pair15_spec_supported(p->geo.n, p->geo.h, p->geo.ring_len) && t.ptw && t.wa &&
+        aligned4(d_x) && crlot::pair15_spec_fits(p->geo.n, ld_x, T))
+        return StftRoute::kPair15;  // N = 960 / 480 frame pairs (K_pair15's transforms; pairing off: the mixed-radix rfft)
+    if (p->pairing && crlot::pairn_spec_supported(p->geo.n, p->geo.h, p->geo.ring_len) && t.ptwn && t.wa &&
+        aligned4(d_x) && T < (int64_t(1) << 27))
+        return StftRoute::kPairN;  // K_pairN's one-wave sizes (882, 1000, 640, 400, 320) (pairing off: the mixed-radix rfft)
+    if (!p->generic && crlot::stft_supported(p->geo.n)) return StftRoute::kWalk;
+    return StftRoute::kStaged;
+}
+
 // x -> spectra; `work` holds S F N floats of windowed frames when the frame size
 // takes the mixed-radix rfft (else unused)
 int stft_impl(crlot_plan* p, const float* d_x, float* d_spec, int32_t n_streams, int64_t T, int64_t ld_x, int64_t F,
               int64_t ld_spec, int64_t ld_frame, float* work, hipStream_t s) {
     const crlot::DevTables t = tables(p);
     hipError_t e;
-    const int64_t lim = int64_t(1) << 29;
-    if (p->pairing && crlot::pair_spec_supported(p->geo.n, p->geo.h) && crlot::pair_tables(p->geo, t) && aligned4(d_x) && T < lim) {
-        // N = 512 - 4096 frame pairs (pairing off: K_stft, bit-identical to crlot_rfft_batched)
-        e = crlot::launch_pair_stft(p->geo, t, d_x, n_streams, T, ld_x, F, d_spec, ld_spec, ld_frame, s);
-        return e == hipSuccess ? CRLOT_OK : hip_fail(e, "stft (frame pairs) kernel launch");
-    }
-    if (p->pairing && crlot::pair15_spec_supported(p->geo.n, p->geo.h, p->geo.ring_len) && t.ptw && t.wa &&
-        aligned4(d_x) && crlot::pair15_spec_fits(p->geo.n, ld_x, T)) {
-        // N = 960 / 480 frame pairs (K_pair15's transforms; pairing off: the mixed-radix rfft below)
-        e = crlot::launch_pair15_stft(p->geo, t, d_x, n_streams, T, ld_x, F, d_spec, ld_spec, ld_frame, s);
-        return e == hipSuccess ? CRLOT_OK : hip_fail(e, "stft (frame pairs, N = 960 / 480) kernel launch");
-    }
-    if (p->pairing && crlot::pairn_spec_supported(p->geo.n, p->geo.h, p->geo.ring_len) && t.ptwn && t.wa &&
-        aligned4(d_x) && T < (int64_t(1) << 27)) {
-        // K_pairN's one-wave sizes (882, 1000, 640, 400, 320) as frame pairs (pairing off: the mixed-radix rfft below)
-        e = crlot::launch_pairn_stft(p->geo, t, d_x, n_streams, T, ld_x, F, d_spec, ld_spec, ld_frame, s);
-        return e == hipSuccess ? CRLOT_OK : hip_fail(e, "stft (frame pairs, K_pairN sizes) kernel launch");
-    }
-    if (!p->generic && crlot::stft_supported(p->geo.n)) {
-        e = crlot::launch_stft(p->geo, t, d_x, n_streams, T, ld_x, F, d_spec, ld_spec, ld_frame, s);
-        return e == hipSuccess ? CRLOT_OK : hip_fail(e, "stft kernel launch");
+    switch (stft_route(p, t, d_x, T, ld_x)) {
+        case StftRoute::kPair:
+            e = crlot::launch_pair_stft(p->geo, t, d_x, n_streams, T, ld_x, F, d_spec, ld_spec, ld_frame, s);
+            return e == hipSuccess ? CRLOT_OK : hip_fail(e, "stft (frame pairs) kernel launch");
+        case StftRoute::kPair15:
+            e = crlot::launch_pair15_stft(p->geo, t, d_x, n_streams, T, ld_x, F, d_spec, ld_spec, ld_frame, s);
+            return e == hipSuccess ? CRLOT_OK : hip_fail(e, "stft (frame pairs, N = 960 / 480) kernel launch");
+        case StftRoute::kPairN:
+            e = crlot::launch_pairn_stft(p->geo, t, d_x, n_streams, T, ld_x, F, d_spec, ld_spec, ld_frame, s);
+            return e == hipSuccess ? CRLOT_OK : hip_fail(e, "stft (frame pairs, K_pairN sizes) kernel launch");
+        case StftRoute::kWalk:
+            e = crlot::launch_stft(p->geo, t, d_x, n_streams, T, ld_x, F, d_spec, ld_spec, ld_frame, s);
+            return e == hipSuccess ? CRLOT_OK : hip_fail(e, "stft kernel launch");
+        case StftRoute::kStaged: break;
     }
     // other sizes: the windowed frames, then IFftPlan::forward on each (crlot_rfft_batched's kernel)
     e = crlot::launch_frames_windowed(p->geo, t, d_x, n_streams, T, ld_x, F, work, s);
@@ -1251,6 +1261,157 @@ int crlot_istft_ola(crlot_plan* p, const float* d_spec, float* d_y, int32_t n_st
         frames = sc->work + sp;
     }
     return istft_impl(p, d_spec, d_y, n_streams, F, ld_spec, ld_frame, ld_y, specw, frames, s);
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------ spectrogram features
+// crlot_stft's analysis half with the feature epilogue (feat.hip): the walkers
+// where crlot_stft itself would run K_stft (N <= 1024) or K_pair_stft (N = 1024),
+// else crlot_stft's own dispatch into a workspace and the staged pass over it.
+struct crlot_features {
+    crlot_plan* plan = nullptr;
+    int device = 0;
+    crlot_features_desc desc{};
+    int32_t n_out = 0, widest = 0, n_w = 0;  // n_w: weights in d_w
+    crlot::FeatBand* d_bands = nullptr;  // [n_bands] spans
+    float* d_w = nullptr;                // the spans' weights, band after band
+};
+
+namespace {
+// the staged form's workspace per slice of streams (one stream's worth if that is more)
+constexpr int64_t kFeatWorkspaceCap = int64_t(256) << 20;
+}  // namespace
+
+extern "C" {
+
+int crlot_features_create(crlot_plan* p, const crlot_features_desc* d, const float* weights, crlot_features** out) {
+    if (!p || !d || !out) return fail(CRLOT_EINVAL, "null argument");
+    *out = nullptr;
+    if (d->kind != CRLOT_FEAT_POWER && d->kind != CRLOT_FEAT_MAGNITUDE) return fail(CRLOT_EINVAL, "unknown feature kind");
+    if (d->log < CRLOT_FEAT_LIN || d->log > CRLOT_FEAT_DB) return fail(CRLOT_EINVAL, "unknown log mode");
+    if (d->n_bands < 0 || d->n_bands > 512) return fail(CRLOT_EINVAL, "n_bands must be 0 .. 512");
+    if ((d->n_bands == 0) != (weights == nullptr))
+        return fail(CRLOT_EINVAL, "weights must be NULL exactly when n_bands is 0");
+    if (d->log != CRLOT_FEAT_LIN && !(std::isfinite(d->floor) && d->floor >= 0x1p-126f))
+        return fail(CRLOT_EINVAL, "floor must be finite and at least FLT_MIN");
+    const int bins = p->geo.n / 2 + 1;
+    for (int64_t i = 0; i < int64_t(d->n_bands) * bins; ++i)
+        if (!std::isfinite(weights[i])) return fail(CRLOT_EINVAL, "non-finite filterbank weight");
+    std::vector<int32_t> lo(d->n_bands), hi(d->n_bands);
+    int rc = crlot_filterbank_spans(weights, d->n_bands, bins, lo.data(), hi.data());
+    if (rc != CRLOT_OK) return rc;
+    std::vector<crlot::FeatBand> bands(d->n_bands);
+    std::vector<float> packed;
+    int32_t widest = 0;
+    for (int j = 0; j < d->n_bands; ++j) {
+        bands[j] = crlot::FeatBand{lo[j], hi[j] - lo[j], int32_t(packed.size()), 0};
+        packed.insert(packed.end(), weights + size_t(j) * bins + lo[j], weights + size_t(j) * bins + hi[j]);
+        widest = std::max(widest, hi[j] - lo[j]);
+    }
+    crlot_features* f = new crlot_features();
+    f->plan = p;
+    f->device = p->device;
+    f->desc = *d;
+    if (d->log == CRLOT_FEAT_LIN) f->desc.floor = 0.0f;
+    f->n_out = d->n_bands ? d->n_bands : bins;
+    f->widest = widest;
+    f->n_w = int32_t(packed.size());
+    if (d->n_bands) {
+        DeviceGuard g(p->device);
+        const size_t bb = sizeof(crlot::FeatBand) * bands.size(), wb = sizeof(float) * std::max<size_t>(1, packed.size());
+        hipError_t e = hipMalloc(reinterpret_cast<void**>(&f->d_bands), bb);
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&f->d_w), wb);
+        if (e == hipSuccess) e = hipMemcpy(f->d_bands, bands.data(), bb, hipMemcpyHostToDevice);
+        if (e == hipSuccess && !packed.empty())
+            e = hipMemcpy(f->d_w, packed.data(), sizeof(float) * packed.size(), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            crlot_features_destroy(f);
+            return hip_fail(e, "filterbank upload");
+        }
+    }
+    *out = f;
+    return CRLOT_OK;
+}
+
+void crlot_features_destroy(crlot_features* f) {
+    if (!f) return;
+    if (f->d_bands || f->d_w) {
+        DeviceGuard g(f->device);
+        if (f->d_bands) (void)hipFree(f->d_bands);  // (hipFree waits for the kernels that read them)
+        if (f->d_w) (void)hipFree(f->d_w);
+    }
+    delete f;
+}
+
+int crlot_features_info(const crlot_features* f, int32_t* n_out, int32_t* kind, int32_t* log_mode, int32_t* widest_band) {
+    if (!f) return fail(CRLOT_EINVAL, "null features object");
+    if (n_out) *n_out = f->n_out;
+    if (kind) *kind = f->desc.kind;
+    if (log_mode) *log_mode = f->desc.log;
+    if (widest_band) *widest_band = f->widest;
+    return CRLOT_OK;
+}
+
+int crlot_spectrogram(crlot_features* f, const float* d_x, float* d_out, int32_t n_streams, int64_t T, int64_t ld_x,
+                      int64_t ld_out, int64_t ld_frame, void* stream) {
+    if (!f) return fail(CRLOT_EINVAL, "null features object");
+    crlot_plan* p = f->plan;
+    if (n_streams < 0 || T < 0) return fail(CRLOT_EINVAL, "negative size");
+    LaunchScope ls(p, stream);
+    const int64_t F = frames_for(p, T);
+    if (n_streams == 0 || F == 0) return CRLOT_OK;
+    if ((!d_x && T > 0) || !d_out) return fail(CRLOT_EINVAL, "null buffer");
+    if (ld_frame < f->n_out) return fail(CRLOT_EINVAL, "ld_frame is smaller than n_out");
+    if (ld_x < T || (n_streams > 1 && ld_out < (F - 1) * ld_frame + f->n_out))
+        return fail(CRLOT_EINVAL, "leading dimension too small");
+    if (!aligned4(d_out)) return fail(CRLOT_EINVAL, "output rows must be 4-byte aligned floats");
+    if (F > INT32_MAX) return fail(CRLOT_EUNSUPPORTED, "too many frames per stream");
+    DeviceGuard g(p->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    std::lock_guard<std::mutex> lk(p->mu);
+    const crlot::DevTables t = tables(p);
+    crlot::FeatDev fd{};
+    fd.out = d_out;
+    fd.ld_out = ld_out;
+    fd.ld_frame = ld_frame;
+    fd.bands = f->d_bands;
+    fd.w = f->d_w;
+    fd.n_bands = f->desc.n_bands;
+    fd.kind = f->desc.kind;
+    fd.log = f->desc.log;
+    fd.floor = f->desc.floor;
+    fd.n_w = f->n_w;
+    const StftRoute route = stft_route(p, t, d_x, T, ld_x);
+    if (route == StftRoute::kPair && crlot::pair_feat_supported(p->geo.n, p->geo.h)) {
+        const hipError_t e = crlot::launch_pair_feat(p->geo, t, fd, d_x, n_streams, T, ld_x, F, s);
+        return e == hipSuccess ? CRLOT_OK : hip_fail(e, "feature (frame pairs) kernel launch");
+    }
+    if (route == StftRoute::kWalk && crlot::feat_walk_supported(p->geo.n)) {
+        const hipError_t e = crlot::launch_feat(p->geo, t, fd, d_x, n_streams, T, ld_x, F, s);
+        return e == hipSuccess ? CRLOT_OK : hip_fail(e, "feature kernel launch");
+    }
+    // staged: crlot_stft's own dispatch into flat rows of N+2 floats, then the feature pass;
+    // the streams in slices whose workspace stays under the cap
+    crlot::Scratch* sc = scratch_slot(p, s);
+    if (!sc) return fail(CRLOT_EHIP, "scratch slot");
+    const int64_t row = p->geo.n + 2;
+    const bool frames = p->generic || !crlot::stft_supported(p->geo.n);  // (as crlot_stft: the mixed-radix rfft's input)
+    const int64_t per_stream = F * (row + (frames ? p->geo.n : 0)) * int64_t(sizeof(float));
+    const int64_t slice = std::max<int64_t>(1, std::min<int64_t>(n_streams, kFeatWorkspaceCap / per_stream));
+    int rc = ensure_workspace(sc, slice * per_stream);
+    if (rc != CRLOT_OK) return rc;
+    float* spec = sc->work;
+    float* work = frames ? spec + slice * F * row : nullptr;
+    for (int64_t s0 = 0; s0 < n_streams; s0 += slice) {
+        const int32_t ns = int32_t(std::min<int64_t>(slice, n_streams - s0));
+        rc = stft_impl(p, d_x + s0 * ld_x, spec, ns, T, ld_x, F, F * row, row, work, s);
+        if (rc != CRLOT_OK) return rc;
+        fd.out = d_out + s0 * ld_out;
+        const hipError_t e = crlot::launch_feat_step(fd, spec, F * row, row, ns, F, p->geo.n / 2 + 1, s);
+        if (e != hipSuccess) return hip_fail(e, "feature step kernel launch");
+    }
+    return CRLOT_OK;
 }
 
 }  // extern "C"

@@ -457,6 +457,45 @@ hipError_t launch_frames_windowed(const Geometry& g, const DevTables& t, const f
 hipError_t launch_spec_step(const DevTables& t, const SpecMask& m, const float* spec, int64_t ld_spec,
                             int64_t ld_frame, float* out, int n_streams, int64_t F, int bins, hipStream_t s);
 
+// ---- feat.hip: fused spectrogram features (crlot_spectrogram)
+// One band of the filterbank on the device: its span [lo, lo + n) of bins and
+// where the span's weights start in the packed weight array.
+struct FeatBand {
+    int32_t lo, n, off, pad;
+};
+
+// What a feature kernel needs beyond the transform's own arguments.
+struct FeatDev {
+    float* out;              // frame k of stream s: out + s ld_out + k ld_frame, n_out floats
+    int64_t ld_out, ld_frame;
+    const FeatBand* bands;   // [n_bands] (nullptr: n_bands == 0)
+    const float* w;          // the spans' weights, band after band
+    int32_t n_bands;         // 0: one value per bin
+    int32_t kind, log;
+    float floor;
+    int32_t n_w;             // weights in w
+};
+// The walkers stage a filterbank of at most this many bytes (spans + weights) in
+// LDS -- k_pair_feat over its twiddle tables, which live in registers after the
+// set-up, k_feat behind its exchange buffers; a larger one is read through L2.
+constexpr int kFeatLdsBytes = 8064;
+__host__ __device__ inline bool feat_bank_in_lds(const FeatDev& f) {
+    return f.n_bands > 0 && int64_t(f.n_bands) * int64_t(sizeof(FeatBand)) + int64_t(f.n_w) * 4 <= kFeatLdsBytes;
+}
+
+// k_feat: K_stft's walk at N = 256 / 512 / 1024 with the feature epilogue; k_pair_feat:
+// K_pair_stft's at N = 1024, H = 128 / 256 / 512 (the pair tables); k_feat_step: the same
+// per-bin and band arithmetic over spectra in HBM (rows of `bins` float pairs, frame k of
+// stream s at spec + s ld_spec + k ld_row)
+bool feat_walk_supported(int n);
+bool pair_feat_supported(int n, int h);
+hipError_t launch_feat(const Geometry& g, const DevTables& t, const FeatDev& f, const float* x, int n_streams,
+                       int64_t T, int64_t ld_x, int64_t F, hipStream_t s);
+hipError_t launch_pair_feat(const Geometry& g, const DevTables& t, const FeatDev& f, const float* x, int n_streams,
+                            int64_t T, int64_t ld_x, int64_t F, hipStream_t s);
+hipError_t launch_feat_step(const FeatDev& f, const float* spec, int64_t ld_spec, int64_t ld_row, int n_streams,
+                            int64_t F, int bins, hipStream_t s);
+
 // dsp::FrameQueue frames on the device: [stream][F][N] from x [stream][ld_x]
 hipError_t launch_fq_frames(const float* x, int64_t T, int64_t ld_x, int n_streams, float* frames, int64_t F,
                             int64_t N, int64_t H, int64_t pad, int pad_mode, hipStream_t s);

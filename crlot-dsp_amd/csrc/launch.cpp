@@ -70,6 +70,9 @@ extern "C" const char* crlot_kernel_name(int32_t id) {
         case CRLOT_K_PAIR_MASK: return "k_pair_mask";
         case CRLOT_K_PAIR_STFT: return "k_pair_stft";
         case CRLOT_K_PAIR_ISTFT: return "k_pair_istft";
+        case CRLOT_K_FEAT: return "k_feat";
+        case CRLOT_K_PAIR_FEAT: return "k_pair_feat";
+        case CRLOT_K_FEAT_STEP: return "k_feat_step";
         case CRLOT_K_EXPERIMENT: return "k_experiment";
         default: return "unknown";
     }

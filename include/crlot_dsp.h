@@ -228,6 +228,9 @@ int crlot_test_inject(int32_t what, int32_t count);
 #define CRLOT_K_PAIR_MASK 29     /* N = 1024 frame-pair walk with the per-frame mask */
 #define CRLOT_K_PAIR_STFT 30     /* crlot_stft as frame pairs (N = 1024) */
 #define CRLOT_K_PAIR_ISTFT 31    /* crlot_istft_ola as frame pairs (N = 1024) */
+#define CRLOT_K_FEAT 32          /* crlot_spectrogram: one frame per wave (N = 256 / 512 / 1024) */
+#define CRLOT_K_PAIR_FEAT 33     /* crlot_spectrogram as frame pairs (N = 1024) */
+#define CRLOT_K_FEAT_STEP 34     /* crlot_spectrogram, staged: features of spectra in HBM */
 #define CRLOT_K_EXPERIMENT 99    /* experiment builds only */
 typedef struct crlot_launch_info {
     int32_t n_kernels;
@@ -362,6 +365,87 @@ int crlot_stft(crlot_plan* plan, const float* d_x, float* d_spec, int32_t n_stre
                int64_t ld_spec, int64_t ld_frame, void* stream);
 int crlot_istft_ola(crlot_plan* plan, const float* d_spec, float* d_y, int32_t n_streams, int64_t F,
                     int64_t ld_spec, int64_t ld_frame, int64_t ld_y, void* stream);
+
+/* ---------------------------------------------------------------- spectrogram features
+ * crlot_stft's analysis half with the feature computed where the spectrum
+ * would be stored: |X|^2, |X| or filterbank bands of them, optionally logged.
+ * The complex spectra never reach HBM where crlot_stft itself would run its
+ * per-wave kernel at N = 256 / 512 / 1024 or its frame-pair kernel at N = 1024
+ * (H = 128 / 256 / 512).  Every other route of crlot_stft stages the spectra
+ * through a bounded workspace, same values: N = 2048 / 4096, the mixed-radix
+ * sizes, and N = 512 at H = 128 / 256 under the default frame pairing (its stft
+ * is the N = 512 frame-pair kernel; with pairing 0 it takes the per-wave walker).
+ *
+ * The value contract.
+ *   Per bin.  X[b] is bit for bit what crlot_stft writes for that frame under the
+ *   plan's current frame-pairing setting (no sanitize after the forward).  Then
+ *     p = fl(fl(re*re) + fl(im*im))     two products and one sum, each rounded to
+ *                                       float32, no FMA; +Inf when it overflows
+ *     CRLOT_FEAT_MAGNITUDE: sqrtf(p), correctly rounded.
+ *   Filterbank.  At creation row j is reduced to its span [lo, hi): the first to
+ *   the last non-zero weight (crlot_filterbank_spans; an all-zero row has
+ *   lo = hi = 0 and yields +0 before the log).  Only the spans' weights live on
+ *   the device.  With v the per-bin value of the chosen kind,
+ *     band j = sum over b in [lo, hi) of fl(w[j][b] * v[b])
+ *   in float32, in this order, fixed per (N, band):
+ *     - span offset i = b - lo belongs to part g = i mod 8; part g adds its terms
+ *       t_i = fl(w_i * v_i) in ascending i starting from +0:
+ *       s_g = (((0 + t_g) + t_{g+8}) + t_{g+16}) + ...   (every sum rounded, no FMA);
+ *     - band = ((s0 + s1) + (s2 + s3)) + ((s4 + s5) + (s6 + s7)).
+ *   Every kernel runs this one order, so output bits never depend on batch size,
+ *   chunking, stream count, ld_*, the kernel chosen (walker or staged) or the
+ *   run.  No float atomics.
+ *   Log.  The value logged is bit for bit the LIN output: logf / log10f /
+ *   10 * log10f of fmaxf(v, floor); a NaN value logs as floor.
+ *
+ * desc.floor is read only when log != CRLOT_FEAT_LIN and must then be finite and
+ * >= FLT_MIN.  weights: host [n_bands][N/2+1] row-major, NULL iff n_bands == 0,
+ * every weight finite.  The plan must outlive the object; several objects may
+ * share a plan.  crlot_spectrogram takes the plan's lock and records its
+ * kernels in crlot_plan_last_launch (CRLOT_K_FEAT / _PAIR_FEAT / _FEAT_STEP;
+ * n_chunks reported as crlot_stft reports it: equal to crlot_stft's under
+ * crlot_plan_set_chunks; the library's own choice follows the residency of the
+ * kernel that runs and may differ).  The staged form slices the streams so that its
+ * workspace (spectra, and the windowed frames of mixed-radix sizes) stays within
+ * 256 MiB, or one stream's worth if that is more. */
+#define CRLOT_FEAT_POWER 0      /* re*re + im*im */
+#define CRLOT_FEAT_MAGNITUDE 1  /* sqrt of that */
+#define CRLOT_FEAT_LIN 0
+#define CRLOT_FEAT_LN 1         /* logf(max(v, floor)) */
+#define CRLOT_FEAT_LOG10 2
+#define CRLOT_FEAT_DB 3         /* 10 * log10f(max(v, floor)) */
+typedef struct crlot_features crlot_features;
+typedef struct crlot_features_desc {
+    int32_t kind;     /* CRLOT_FEAT_POWER / _MAGNITUDE */
+    int32_t n_bands;  /* 0: one value per bin, n_out = N/2+1; 1..512: filterbank rows, n_out = n_bands */
+    int32_t log;      /* CRLOT_FEAT_LIN / _LN / _LOG10 / _DB */
+    float floor;      /* log != LIN: finite and >= FLT_MIN; a NaN value logs as floor (fmaxf) */
+} crlot_features_desc;
+/* weights: host [n_bands][N/2+1] row-major, NULL iff n_bands == 0; the plan must outlive the object */
+int crlot_features_create(crlot_plan* plan, const crlot_features_desc* desc, const float* weights,
+                          crlot_features** out);
+void crlot_features_destroy(crlot_features* f);
+/* any of the outputs may be NULL; widest_band: the longest span (0 without a filterbank) */
+int crlot_features_info(const crlot_features* f, int32_t* n_out, int32_t* kind, int32_t* log_mode,
+                        int32_t* widest_band);
+/* frame k of stream s (framing, window, sanitize, forward exactly as crlot_stft): n_out floats at
+ * d_out[s*ld_out + k*ld_frame + j]; ld_frame >= n_out; F = crlot_frame_count(T).  F == 0 or
+ * n_streams == 0: CRLOT_OK, nothing written. */
+int crlot_spectrogram(crlot_features* f, const float* d_x, float* d_out, int32_t n_streams, int64_t T,
+                      int64_t ld_x, int64_t ld_out, int64_t ld_frame, void* stream);
+/* host helpers (no device) */
+#define CRLOT_MEL_HTK 0
+#define CRLOT_MEL_SLANEY 1
+/* Triangular mel filterbank, computed in double and rounded once to float: n_mels + 2 points
+ * equally spaced on the mel scale between fmin and fmax (fmax <= 0: sample_rate / 2); HTK
+ * mel = 2595 log10(1 + f/700); Slaney linear f / (200/3) below 1000 Hz, logarithmic above with
+ * step ln(6.4)/27.  Bin b has frequency b sample_rate / nfft and weight
+ * max(0, min((f - f_lo)/(f_c - f_lo), (f_hi - f)/(f_hi - f_c))); slaney_norm multiplies row j by
+ * 2/(f_hi - f_lo).  CRLOT_EINVAL: n_mels < 1, nfft odd or < 2, not 0 <= fmin < fmax <= sample_rate/2. */
+int crlot_mel_filterbank(int32_t n_mels, int32_t nfft, double sample_rate, double fmin, double fmax,
+                         int32_t scale, int32_t slaney_norm, float* out /* [n_mels][nfft/2+1] */);
+/* lo[j], hi[j]: row j's span (first to one past the last non-zero weight; all zero: 0, 0) */
+int crlot_filterbank_spans(const float* weights, int32_t n_bands, int32_t bins, int32_t* lo, int32_t* hi);
 
 /* Batched IFftPlan::forward / inverse with the adapter's semantics
  * (kissfft_adapter.cc:83-168): forward sanitizes its input, inverse scales by

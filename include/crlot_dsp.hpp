@@ -203,6 +203,48 @@ class StftEngine {
     DeviceBuffer<float> dx_, dy_;
 };
 
+// Spectrogram features of a plan's STFT (crlot_features_*): per bin |X|^2 / |X|
+// (weights null), or n_bands filterbank rows [n_bands][frame_size/2 + 1] of them,
+// optionally logged.  The plan (an StftEngine's plan()) must outlive the object.
+class Features {
+   public:
+    Features(crlot_plan* plan, int kind = CRLOT_FEAT_POWER, const float* weights = nullptr, int n_bands = 0,
+             int log = CRLOT_FEAT_LIN, float floor = 0.0f) {
+        crlot_features_desc d{};
+        d.kind = kind;
+        d.n_bands = n_bands;
+        d.log = log;
+        d.floor = floor;
+        check(crlot_features_create(plan, &d, weights, &f_), "crlot_features_create");
+    }
+    ~Features() { crlot_features_destroy(f_); }
+    Features(const Features&) = delete;
+    Features& operator=(const Features&) = delete;
+    Features(Features&& o) noexcept : f_(o.f_) { o.f_ = nullptr; }
+    Features& operator=(Features&& o) noexcept {
+        if (this != &o) {
+            crlot_features_destroy(f_);
+            f_ = o.f_;
+            o.f_ = nullptr;
+        }
+        return *this;
+    }
+    int n_out() const {
+        int32_t n = 0;
+        check(crlot_features_info(f_, &n, nullptr, nullptr, nullptr), "crlot_features_info");
+        return n;
+    }
+    // frame k of stream s: n_out() floats at d_out + s*ld_out + k*ld_frame (ld_frame >= n_out())
+    void spectrogram_device(const float* d_x, float* d_out, int n_streams, int64_t T, int64_t ld_x, int64_t ld_out,
+                            int64_t ld_frame, hipStream_t s = nullptr) {
+        check(crlot_spectrogram(f_, d_x, d_out, n_streams, T, ld_x, ld_out, ld_frame, s), "crlot_spectrogram");
+    }
+    crlot_features* get() const { return f_; }
+
+   private:
+    crlot_features* f_ = nullptr;
+};
+
 // Real-time per-hop streaming with hops in host memory (BASELINE config 4):
 // the resident kernel behind crlot_stream_rt_*.  push_hop copies one hop of
 // channels x H samples in ([H][C] interleaved PCM or [C][H]), returns the H
