@@ -450,9 +450,176 @@ bool istft_walk_ok(const crlot_plan* p, const float* y, int64_t ld_y) {
            p->fast_ok && aligned8(y) && ld_y % 2 == 0;
 }
 
-// (x rows may be 4-byte aligned only: the walk's frame loads check the alignment per frame)
-bool masked_walk_ok(const crlot_plan* p, const float* y, int64_t ld_y) {
-    return istft_walk_ok(p, y, ld_y) && (p->geo.pad & 1) == 0;
+// ------------------------------------------------------------------ routes
+// Which kernels a call runs and what scratch they take, decided in one place per
+// entry from the plan, its tables and the call's buffers: the entries switch on
+// the route, crlot_plan_reserve_stream reads the sizes of the same route.
+enum class RouteKind {
+    kFused,     // crlot_roundtrip: K_fused* / K_pair / K_pair512 / K_pair2k (launch_fused)
+    kFusedWg,   // ... the workgroup walkers, K_pair4k (launch_fused_wg)
+    kFusedAny,  // ... the any-size walker alone
+    kPair30,    // ... K_pair30, then the any-size walker over the flagged streams
+    kPair15,    // 960 / 480: K_pair15 and that redo (crlot_roundtrip) or its spectral walkers
+    kPairN,     // K_pairN's sizes: the same
+    kPair,      // the spectral entries: power-of-two frame pairs (N = 512 - 4096)
+    kWalk,      // ... one frame per wave / workgroup (K_stft, K_istft)
+    kStaged,    // frames and / or spectra through the workspace
+};
+struct Route {
+    RouteKind kind = RouteKind::kStaged;
+    bool needs_flags = false;  // the per-walker regime flags (ensure_pair_flags)
+    int64_t work_bytes = 0;    // Scratch::work
+};
+
+// The buffers a walker touches: the input side (T samples per stream) and / or the
+// output side (out_len samples per stream).
+struct Sides {
+    bool in = false, out = false;
+    const float* x = nullptr;
+    int64_t ld_x = 0, T = 0;
+    const float* y = nullptr;
+    int64_t ld_y = 0, out_len = 0;
+    int32_t n_streams = 0;
+};
+Sides in_side(const float* x, int64_t ld_x, int64_t T) {
+    Sides s;
+    s.in = true;
+    s.x = x;
+    s.ld_x = ld_x;
+    s.T = T;
+    return s;
+}
+Sides both_sides(const float* x, int64_t ld_x, int64_t T, const float* y, int64_t ld_y, int64_t out_len,
+                 int32_t n_streams) {
+    Sides s = in_side(x, ld_x, T);
+    s.out = true;
+    s.y = y;
+    s.ld_y = ld_y;
+    s.out_len = out_len;
+    s.n_streams = n_streams;
+    return s;
+}
+Sides out_side(const float* y, int64_t ld_y, int64_t out_len) {
+    Sides s = both_sides(nullptr, 0, 0, y, ld_y, out_len, 0);
+    s.in = false;
+    return s;
+}
+
+// One predicate per kernel family: pairing on, the shape supported, the tables the
+// family reads, 4- or 8-byte alignment, and the extent its 32-bit offsets cover
+// (2^29 floats with buffer descriptors of 4-byte elements, 2^27 where one
+// descriptor spans more than a stream; tests/test_gpu_extents.py).
+constexpr int64_t kLim27 = int64_t(1) << 27, kLim29 = int64_t(1) << 29;
+
+// crlot_roundtrip's fused walkers, power-of-two N: every byte offset of a stream
+// (input and output) below 2^31.  K_pair (N = 1024 frame pairs) moves single
+// floats: any 4-byte-aligned rows take it, so a stream's bits do not depend on the
+// parity of its row stride; the other fused walkers move float2.
+bool fused_family(const crlot_plan* p, const crlot::DevTables& t, const Sides& s) {
+    const crlot::Geometry& g = p->geo;
+    const bool layout_ok = crlot::pair1k_plan(g, t)
+                               ? aligned4(s.x) && aligned4(s.y)
+                               : aligned8(s.x) && aligned8(s.y) && s.ld_x % 2 == 0 && s.ld_y % 2 == 0;
+    return (crlot::fused_supported(g.n, g.h) || crlot::fused_wg_supported(g.n, g.h)) && g.ring_len % g.h == 0 &&
+           layout_ok && s.T < kLim29 && s.out_len + 2 * g.n < kLim29 && int64_t(s.n_streams) * (s.T / g.h + 1) < kLim29;
+}
+// crlot_roundtrip's any-size walker (no alignment demands), and the paired-only
+// walkers that run ahead of it: zero padding, their tables, 2^27 extents
+bool fused_any_family(const crlot_plan* p, const Sides& s) {
+    return p->generic && crlot::fused_any_fits(p->geo.n, p->geo.h) && s.ld_x < (int64_t(1) << 40);
+}
+bool pair_walker_common(const crlot_plan* p, const crlot::DevTables& t, const Sides& s) {
+    return p->pairing && t.ptw && p->geo.pad_mode == 0 && s.T < kLim27 && s.out_len < kLim27;
+}
+bool pair15_walker_family(const crlot_plan* p, const crlot::DevTables& t, const Sides& s) {
+    return pair_walker_common(p, t, s) && !crlot::pairn_over_pair15(p->geo.n) &&
+           crlot::pair15_supported(p->geo.n, p->geo.h, p->geo.ring_len) && s.ld_x < kLim27 && s.ld_y < kLim27;
+}
+bool pair30_walker_family(const crlot_plan* p, const crlot::DevTables& t, const Sides& s) {
+    return pair_walker_common(p, t, s) && p->pair30;
+}
+bool pairn_walker_family(const crlot_plan* p, const crlot::DevTables& t, const Sides& s) {
+    return pair_walker_common(p, t, s) && !p->pair30 &&
+           crlot::pairn_supported(p->geo.n, p->geo.h, p->geo.ring_len);
+}
+// The spectral entries (crlot_stft: the input side; crlot_istft_ola: the output
+// side; the masked crlot_roundtrip: both).  N = 512 - 4096 frame pairs:
+bool pair_spec_family(const crlot_plan* p, const crlot::DevTables& t, const Sides& s) {
+    const crlot::Geometry& g = p->geo;
+    if (!p->pairing || !crlot::pair_spec_supported(g.n, g.h) || !crlot::pair_tables(g, t)) return false;
+    if (s.in && !(aligned4(s.x) && s.T < kLim29)) return false;
+    if (s.out && !(g.ring_len % g.h == 0 && aligned4(s.y) && s.out_len + 2 * g.n < kLim29)) return false;
+    return !(s.in && s.out) || int64_t(s.n_streams) * (s.T / g.h + 1) < kLim29;
+}
+// N = 960 / 480 frame pairs (K_pair15's transforms)
+bool pair15_spec_family(const crlot_plan* p, const crlot::DevTables& t, const Sides& s) {
+    const crlot::Geometry& g = p->geo;
+    if (!p->pairing || !crlot::pair15_spec_supported(g.n, g.h, g.ring_len) || !t.ptw) return false;
+    if (s.in && !(t.wa && aligned4(s.x) && crlot::pair15_spec_fits(g.n, s.ld_x, s.T))) return false;
+    return !s.out || (t.ws && t.den && aligned4(s.y) && crlot::pair15_spec_fits(g.n, s.ld_y, s.out_len + g.n));
+}
+// K_pairN's sizes (882, 1000, 640, 400, 320; 1764, 1920) as frame pairs
+bool pairn_spec_family(const crlot_plan* p, const crlot::DevTables& t, const Sides& s) {
+    const crlot::Geometry& g = p->geo;
+    if (!p->pairing || !crlot::pairn_spec_supported(g.n, g.h, g.ring_len) || !t.ptwn) return false;
+    if (s.in && !(t.wa && aligned4(s.x) && s.T < kLim27)) return false;
+    return !s.out || (t.ws && t.den && aligned4(s.y) && s.out_len + g.n < kLim27);
+}
+// one frame per wave / workgroup: K_stft any power-of-two N; K_istft's walk as
+// istft_walk_ok; from x to y in one walk (x rows may be 4-byte aligned only: the
+// walk's frame loads check the alignment per frame) with an even padding
+bool frame_walk_family(const crlot_plan* p, const Sides& s) {
+    if (s.in && !(!p->generic && crlot::stft_supported(p->geo.n))) return false;
+    if (s.out && !istft_walk_ok(p, s.y, s.ld_y)) return false;
+    return !(s.in && s.out) || (p->geo.pad & 1) == 0;
+}
+
+// The spectral entries' route over `s`.  A staged call's workspace: the N floats of
+// each windowed / inverse frame, with an output side also its stepped spectrum (N + 2)
+Route spectral_route(const crlot_plan* p, const crlot::DevTables& t, const Sides& s, int32_t n_streams, int64_t F) {
+    Route r;
+    if (pair_spec_family(p, t, s)) r.kind = RouteKind::kPair;  // (pairing off: the per-frame walk, bit-identical)
+    else if (pair15_spec_family(p, t, s)) r.kind = RouteKind::kPair15;  // (pairing off: the mixed-radix transforms)
+    else if (pairn_spec_family(p, t, s)) r.kind = RouteKind::kPairN;
+    else if (frame_walk_family(p, s)) r.kind = RouteKind::kWalk;
+    else r.work_bytes = int64_t(n_streams) * F * (p->geo.n + (s.out ? p->geo.n + 2 : 0)) * int64_t(sizeof(float));
+    return r;
+}
+// crlot_stft (crlot_spectrogram follows the same choice, so its spectrum is crlot_stft's bit for bit)
+Route stft_route(const crlot_plan* p, const crlot::DevTables& t, const float* d_x, int64_t T, int64_t ld_x,
+                 int32_t n_streams, int64_t F) {
+    return spectral_route(p, t, in_side(d_x, ld_x, T), n_streams, F);
+}
+Route istft_route(const crlot_plan* p, const crlot::DevTables& t, const float* d_y, int64_t F, int64_t ld_y,
+                  int32_t n_streams) {
+    return spectral_route(p, t, out_side(d_y, ld_y, F * p->geo.h), n_streams, F);
+}
+// the masked crlot_roundtrip: one walk, or crlot_stft and crlot_istft_ola through the workspace
+Route masked_route(const crlot_plan* p, const crlot::DevTables& t, const float* d_x, const float* d_y,
+                   int32_t n_streams, int64_t T, int64_t ld_x, int64_t ld_y, int64_t F) {
+    return spectral_route(p, t, both_sides(d_x, ld_x, T, d_y, ld_y, F * p->geo.h, n_streams), n_streams, F);
+}
+Route roundtrip_route(const crlot_plan* p, const crlot::DevTables& t, const float* d_x, const float* d_y,
+                      int32_t n_streams, int64_t T, int64_t ld_x, int64_t ld_y, int64_t F) {
+    if (p->mask.p) return masked_route(p, t, d_x, d_y, n_streams, T, ld_x, ld_y, F);
+    const Sides s = both_sides(d_x, ld_x, T, d_y, ld_y, F * p->geo.h, n_streams);
+    Route r;
+    r.needs_flags = true;
+    if (fused_family(p, t, s)) {
+        r.kind = crlot::fused_wg_supported(p->geo.n, p->geo.h) ? RouteKind::kFusedWg : RouteKind::kFused;
+    } else if (fused_any_family(p, s)) {
+        if (pair15_walker_family(p, t, s)) r.kind = RouteKind::kPair15;
+        else if (pair30_walker_family(p, t, s)) r.kind = RouteKind::kPair30;
+        else if (pairn_walker_family(p, t, s)) r.kind = RouteKind::kPairN;
+        else {
+            r.kind = RouteKind::kFusedAny;
+            r.needs_flags = false;
+        }
+    } else {
+        r.needs_flags = false;
+        r.work_bytes = int64_t(n_streams) * F * p->geo.n * int64_t(sizeof(float));
+    }
+    return r;
 }
 
 
@@ -732,24 +899,6 @@ int64_t crlot_output_length(const crlot_plan* p, int64_t T) {
     return frames_for(p, T) * p->geo.h;
 }
 
-// The fused kernel addresses a stream with 32-bit buffer offsets: keep every
-// byte offset of a stream (input and output) below 2^31.
-static bool use_fused(const crlot_plan* p, const float* x, const float* y, int64_t ld_x,
-                      int64_t ld_y, int32_t n_streams, int64_t T, int64_t out_len) {
-    const int64_t lim = int64_t(1) << 29;
-    // K_pair (N = 1024 frame pairs) moves single floats: any 4-byte-aligned rows
-    // take it, so a stream's bits do not depend on the parity of its row stride;
-    // the other fused walkers move float2
-    const crlot::DevTables t = tables(p);
-    const bool pair1k = p->geo.n == 1024 && t.ptw && t.pden && t.wsn && t.rden;
-    const bool layout_ok = pair1k ? aligned4(x) && aligned4(y)
-                                  : aligned8(x) && aligned8(y) && ld_x % 2 == 0 && ld_y % 2 == 0;
-    return (crlot::fused_supported(p->geo.n, p->geo.h) ||
-            crlot::fused_wg_supported(p->geo.n, p->geo.h)) &&
-           p->geo.ring_len % p->geo.h == 0 && layout_ok && T < lim &&
-           out_len + 2 * p->geo.n < lim && int64_t(n_streams) * (T / p->geo.h + 1) < lim;
-}
-
 int64_t crlot_workspace_bytes(const crlot_plan* p, int32_t n_streams, int64_t T) {
     if (!p || n_streams < 0 || T < 0) return fail(CRLOT_EINVAL, "bad argument");
     return int64_t(n_streams) * frames_for(p, T) * p->geo.n * int64_t(sizeof(float));
@@ -767,20 +916,17 @@ int crlot_plan_reserve(crlot_plan* p, int64_t bytes) {
     return e == hipSuccess ? CRLOT_OK : hip_fail(e, "workspace reserve");
 }
 
-// The scratch a round trip of this shape takes (aligned rows, ld = T / F*H).
+// The scratch a round trip of this shape takes (aligned rows, ld = T / F*H): the
+// route of the call itself, over a probe pointer.
 static void scratch_need(const crlot_plan* p, int32_t n_streams, int64_t T, int32_t channels, int64_t* flags,
                          int64_t* work, int64_t* planes) {
     const int64_t F = frames_for(p, T), S = int64_t(n_streams) * channels, L = F * p->geo.h;
-    *flags = pair_plan(p) ? 2 * S * std::max<int64_t>(F, 2) : 0;  // as ensure_pair_flags
-    const bool direct_ilv = channels > 1 && channels <= 5 && p->geo.n == 1024 && p->geo.pad_mode == 0;
+    const bool direct_ilv = channels > 1 && channels <= 5 && p->geo.n == 1024 && p->geo.pad_mode == 0 && !p->mask.p;
     *planes = (channels > 1 && !direct_ilv) ? S * (T + L) * int64_t(sizeof(float)) : 0;
     static const float probe[2] = {0.f, 0.f};
-    const bool fused = use_fused(p, probe, const_cast<float*>(probe), T + (T & 1), L + (L & 1), int32_t(S), T, L);
-    const bool any = p->generic && crlot::fused_any_fits(p->geo.n, p->geo.h);
-    *work = (fused || any) ? 0 : S * F * p->geo.n * int64_t(sizeof(float));
-    if (p->mask.p)  // the masked round trip: one walk, or spectra + frames through HBM
-        *work = masked_walk_ok(p, probe, L + (L & 1)) ? 0
-                                                                        : S * F * (2 * p->geo.n + 2) * int64_t(sizeof(float));
+    const Route r = roundtrip_route(p, tables(p), probe, probe, int32_t(S), T, T + (T & 1), L + (L & 1), F);
+    *flags = r.needs_flags && pair_plan(p) ? 2 * S * std::max<int64_t>(F, 2) : 0;  // as ensure_pair_flags
+    *work = r.work_bytes;
 }
 
 int crlot_plan_reserve_stream(crlot_plan* p, int32_t n_streams, int64_t T, int32_t channels, void* stream) {
@@ -810,80 +956,45 @@ static int roundtrip_impl(crlot_plan* p, crlot::Scratch* sc, const float* d_x, f
                           int64_t T, int64_t ld_x, int64_t ld_y, int64_t F, hipStream_t s) {
     if (p->mask.p) return masked_roundtrip(p, sc, d_x, d_y, n_streams, T, ld_x, ld_y, F, s);
     const int64_t out_len = F * p->geo.h;
-    hipError_t e;
-    const bool fused = use_fused(p, d_x, d_y, ld_x, ld_y, n_streams, T, out_len);
-    if (fused) {
-        const int rcf = ensure_pair_flags(p, sc, n_streams, F);
-        if (rcf != CRLOT_OK) return rcf;
-    }
-    const crlot::DevTables t = tables(p, sc);
-    if (fused) {
-        e = !crlot::fused_wg_supported(p->geo.n, p->geo.h)
-                ? crlot::launch_fused(p->geo, t, d_x, d_y, n_streams, T, ld_x, ld_y, F, out_len, s)
-                : crlot::launch_fused_wg(p->geo, t, d_x, d_y, n_streams, T, ld_x, ld_y, F, out_len, s);
-        if (e != hipSuccess) return hip_fail(e, "fused kernel launch");
-        return CRLOT_OK;
-    }
-    if (p->generic && crlot::fused_any_fits(p->geo.n, p->geo.h) && ld_x < (int64_t(1) << 40)) {
-        // N = 960 / 480 frame pairs (K_pair15), then the per-frame walker over the streams it flagged
-        const int64_t lim = int64_t(1) << 27;
-        if (p->pairing && t.ptw && p->geo.pad_mode == 0 && !crlot::pairn_over_pair15(p->geo.n) &&
-            crlot::pair15_supported(p->geo.n, p->geo.h, p->geo.ring_len) && T < lim && out_len < lim &&
-            ld_x < lim && ld_y < lim) {
-            const int rcf = ensure_pair_flags(p, sc, n_streams, F);
-            if (rcf != CRLOT_OK) return rcf;
-            const crlot::DevTables tp = tables(p, sc);
-            int nch = 0, per = 1;
-            e = crlot::launch_pair15(p->geo, tp, d_x, d_y, n_streams, T, ld_x, ld_y, F, out_len, &nch, &per, s);
-            if (e != hipSuccess) return hip_fail(e, "pair (N = 15 L) kernel launch");
-            e = crlot::launch_fused_any(p->geo, tp, p->d_twany, d_x, d_y, n_streams, T, ld_x, ld_y, F, s,
-                                        tp.pflags, nch, per);
-            if (e != hipSuccess) return hip_fail(e, "fused (any size) kernel launch");
-            return CRLOT_OK;
-        }
-        // N = 1920 with an even hop: two 960-point transforms on two waves (K_pair30), the same redo
-        if (p->pairing && t.ptw && p->geo.pad_mode == 0 && p->pair30 && T < lim && out_len < lim) {
-            const int rcf = ensure_pair_flags(p, sc, n_streams, F);
-            if (rcf != CRLOT_OK) return rcf;
-            const crlot::DevTables tp = tables(p, sc);
-            int nch = 0;
-            e = crlot::launch_pair30(p->geo, tp, d_x, d_y, n_streams, T, ld_x, ld_y, F, out_len, &nch, s);
-            if (e != hipSuccess) return hip_fail(e, "pair (N = 1920) kernel launch");
-            e = crlot::launch_fused_any(p->geo, tp, p->d_twany, d_x, d_y, n_streams, T, ld_x, ld_y, F, s,
-                                        tp.pflags, nch, 1);
-            if (e != hipSuccess) return hip_fail(e, "fused (any size) kernel launch");
-            return CRLOT_OK;
-        }
-        // N = 320 ... 1764 with factors 2, 3, 5, 7 (K_pairN), then the same redo
-        if (p->pairing && t.ptw && p->geo.pad_mode == 0 && !p->pair30 &&
-            crlot::pairn_supported(p->geo.n, p->geo.h, p->geo.ring_len) && T < lim && out_len < lim) {
-            const int rcf = ensure_pair_flags(p, sc, n_streams, F);
-            if (rcf != CRLOT_OK) return rcf;
-            const crlot::DevTables tp = tables(p, sc);
-            int nch = 0;
-            e = crlot::launch_pairn(p->geo, tp, d_x, d_y, n_streams, T, ld_x, ld_y, F, out_len, &nch, s);
-            if (e != hipSuccess) return hip_fail(e, "pair (N = 2^a 3^b 5^c 7^d) kernel launch");
-            e = crlot::launch_fused_any(p->geo, tp, p->d_twany, d_x, d_y, n_streams, T, ld_x, ld_y, F, s,
-                                        tp.pflags, nch, 1);
-            if (e != hipSuccess) return hip_fail(e, "fused (any size) kernel launch");
-            return CRLOT_OK;
-        }
-        e = crlot::launch_fused_any(p->geo, t, p->d_twany, d_x, d_y, n_streams, T, ld_x, ld_y, F, s);
-        if (e != hipSuccess) return hip_fail(e, "fused (any size) kernel launch");
-        return CRLOT_OK;
-    }
-    const int64_t need = int64_t(n_streams) * F * p->geo.n * int64_t(sizeof(float));
-    int rc = ensure_workspace(sc, need);
+    const crlot::Geometry& g = p->geo;
+    const Route r = roundtrip_route(p, tables(p), d_x, d_y, n_streams, T, ld_x, ld_y, F);
+    int rc = r.needs_flags ? ensure_pair_flags(p, sc, n_streams, F) : ensure_workspace(sc, r.work_bytes);
     if (rc != CRLOT_OK) return rc;
-    e = p->generic ? crlot::launch_synth_any(p->geo, t, p->d_twany, d_x, n_streams, T, ld_x, F,
-                                             sc->work, nullptr, s)
-                   : crlot::launch_synth_frames(p->geo, t, d_x, n_streams, T, ld_x, F, sc->work,
-                                                nullptr, s);
-    if (e != hipSuccess) return hip_fail(e, "synth kernel launch");
-    e = crlot::launch_ola_gather(p->geo, t, sc->work, p->geo.n, d_y, n_streams, F, ld_y,
-                                 out_len, s);
-    if (e != hipSuccess) return hip_fail(e, "gather kernel launch");
-    return CRLOT_OK;
+    const crlot::DevTables t = tables(p, sc);
+    hipError_t e;
+    int nch = 0, per = 1;  // the pair walker's flags per stream and streams per walk
+    switch (r.kind) {
+        case RouteKind::kFused:
+            e = crlot::launch_fused(g, t, d_x, d_y, n_streams, T, ld_x, ld_y, F, out_len, s);
+            return e == hipSuccess ? CRLOT_OK : hip_fail(e, "fused kernel launch");
+        case RouteKind::kFusedWg:
+            e = crlot::launch_fused_wg(g, t, d_x, d_y, n_streams, T, ld_x, ld_y, F, out_len, s);
+            return e == hipSuccess ? CRLOT_OK : hip_fail(e, "fused kernel launch");
+        // the paired-only walker of the size, then the per-frame walker over the streams it flagged
+        case RouteKind::kPair15:  // N = 960 / 480
+            e = crlot::launch_pair15(g, t, d_x, d_y, n_streams, T, ld_x, ld_y, F, out_len, &nch, &per, s);
+            if (e != hipSuccess) return hip_fail(e, "pair (N = 15 L) kernel launch");
+            break;
+        case RouteKind::kPair30:  // N = 1920 with an even hop: two 960-point transforms on two waves
+            e = crlot::launch_pair30(g, t, d_x, d_y, n_streams, T, ld_x, ld_y, F, out_len, &nch, s);
+            if (e != hipSuccess) return hip_fail(e, "pair (N = 1920) kernel launch");
+            break;
+        case RouteKind::kPairN:  // N = 320 ... 1764 with factors 2, 3, 5, 7
+            e = crlot::launch_pairn(g, t, d_x, d_y, n_streams, T, ld_x, ld_y, F, out_len, &nch, s);
+            if (e != hipSuccess) return hip_fail(e, "pair (N = 2^a 3^b 5^c 7^d) kernel launch");
+            break;
+        case RouteKind::kFusedAny: break;
+        default:  // staged
+            e = p->generic ? crlot::launch_synth_any(g, t, p->d_twany, d_x, n_streams, T, ld_x, F, sc->work, nullptr, s)
+                           : crlot::launch_synth_frames(g, t, d_x, n_streams, T, ld_x, F, sc->work, nullptr, s);
+            if (e != hipSuccess) return hip_fail(e, "synth kernel launch");
+            e = crlot::launch_ola_gather(g, t, sc->work, g.n, d_y, n_streams, F, ld_y, out_len, s);
+            return e == hipSuccess ? CRLOT_OK : hip_fail(e, "gather kernel launch");
+    }
+    e = r.kind == RouteKind::kFusedAny
+            ? crlot::launch_fused_any(g, t, p->d_twany, d_x, d_y, n_streams, T, ld_x, ld_y, F, s)
+            : crlot::launch_fused_any(g, t, p->d_twany, d_x, d_y, n_streams, T, ld_x, ld_y, F, s, t.pflags, nch, per);
+    return e == hipSuccess ? CRLOT_OK : hip_fail(e, "fused (any size) kernel launch");
 }
 
 int crlot_roundtrip(crlot_plan* p, const float* d_x, float* d_y, int32_t n_streams, int64_t T,
@@ -1039,43 +1150,26 @@ int crlot_irfft_batched(crlot_plan* p, const float* d_in, float* d_out, int32_t 
 // crlot_istft_ola(crlot_stft(x)) bit for bit.
 namespace {
 
-// Which kernels crlot_stft runs for this plan and input (crlot_spectrogram follows
-// the same choice, so its spectrum is crlot_stft's bit for bit).
-enum class StftRoute { kPair, kPair15, kPairN, kWalk, kStaged };
-StftRoute stft_route(const crlot_plan* p, const crlot::DevTables& t, const float* d_x, int64_t T, int64_t ld_x) {
-    const int64_t lim = int64_t(1) << 29;
-    if (p->pairing && crlot::pair_spec_supported(p->geo.n, p->geo.h) && crlot::pair_tables(p->geo, t) && aligned4(d_x) && T < lim)
-        return StftRoute::kPair;  // N = 512 - 4096 frame pairs (pairing off: K_stft, bit-identical to crlot_rfft_batched)
-    if (p->pairing && crlot::pair15_spec_supported(p->geo.n, p->geo.h, p->geo.ring_len) && t.ptw && t.wa &&
-        aligned4(d_x) && crlot::pair15_spec_fits(p->geo.n, ld_x, T))
-        return StftRoute::kPair15;  // N = 960 / 480 frame pairs (K_pair15's transforms; pairing off: the mixed-radix rfft)
-    if (p->pairing && crlot::pairn_spec_supported(p->geo.n, p->geo.h, p->geo.ring_len) && t.ptwn && t.wa &&
-        aligned4(d_x) && T < (int64_t(1) << 27))
-        return StftRoute::kPairN;  // K_pairN's one-wave sizes (882, 1000, 640, 400, 320) (pairing off: the mixed-radix rfft)
-    if (!p->generic && crlot::stft_supported(p->geo.n)) return StftRoute::kWalk;
-    return StftRoute::kStaged;
-}
-
 // x -> spectra; `work` holds S F N floats of windowed frames when the frame size
 // takes the mixed-radix rfft (else unused)
 int stft_impl(crlot_plan* p, const float* d_x, float* d_spec, int32_t n_streams, int64_t T, int64_t ld_x, int64_t F,
               int64_t ld_spec, int64_t ld_frame, float* work, hipStream_t s) {
     const crlot::DevTables t = tables(p);
     hipError_t e;
-    switch (stft_route(p, t, d_x, T, ld_x)) {
-        case StftRoute::kPair:
+    switch (stft_route(p, t, d_x, T, ld_x, n_streams, F).kind) {
+        case RouteKind::kPair:
             e = crlot::launch_pair_stft(p->geo, t, d_x, n_streams, T, ld_x, F, d_spec, ld_spec, ld_frame, s);
             return e == hipSuccess ? CRLOT_OK : hip_fail(e, "stft (frame pairs) kernel launch");
-        case StftRoute::kPair15:
+        case RouteKind::kPair15:
             e = crlot::launch_pair15_stft(p->geo, t, d_x, n_streams, T, ld_x, F, d_spec, ld_spec, ld_frame, s);
             return e == hipSuccess ? CRLOT_OK : hip_fail(e, "stft (frame pairs, N = 960 / 480) kernel launch");
-        case StftRoute::kPairN:
+        case RouteKind::kPairN:
             e = crlot::launch_pairn_stft(p->geo, t, d_x, n_streams, T, ld_x, F, d_spec, ld_spec, ld_frame, s);
             return e == hipSuccess ? CRLOT_OK : hip_fail(e, "stft (frame pairs, K_pairN sizes) kernel launch");
-        case StftRoute::kWalk:
+        case RouteKind::kWalk:
             e = crlot::launch_stft(p->geo, t, d_x, n_streams, T, ld_x, F, d_spec, ld_spec, ld_frame, s);
             return e == hipSuccess ? CRLOT_OK : hip_fail(e, "stft kernel launch");
-        case StftRoute::kStaged: break;
+        default: break;  // staged
     }
     // other sizes: the windowed frames, then IFftPlan::forward on each (crlot_rfft_batched's kernel)
     e = crlot::launch_frames_windowed(p->geo, t, d_x, n_streams, T, ld_x, F, work, s);
@@ -1101,27 +1195,20 @@ int istft_impl(crlot_plan* p, const float* d_spec, float* d_y, int32_t n_streams
                int64_t ld_frame, int64_t ld_y, float* specw, float* frames, hipStream_t s) {
     const crlot::DevTables t = tables(p);
     hipError_t e;
-    if (p->pairing && crlot::pair_spec_supported(p->geo.n, p->geo.h) && crlot::pair_tables(p->geo, t) &&
-        p->geo.ring_len % p->geo.h == 0 && aligned4(d_y) && F * p->geo.h + 2 * p->geo.n < (int64_t(1) << 29)) {
-        // N = 512 - 4096 frame pairs (pairing off: K_istft, bit-identical to irfft + gather)
-        e = crlot::launch_pair_istft(p->geo, t, p->mask, d_spec, ld_spec, ld_frame, d_y, n_streams, F, ld_y, s);
-        return e == hipSuccess ? CRLOT_OK : hip_fail(e, "istft (frame pairs) kernel launch");
-    }
-    if (p->pairing && crlot::pair15_spec_supported(p->geo.n, p->geo.h, p->geo.ring_len) && t.ptw && t.ws && t.den &&
-        aligned4(d_y) && crlot::pair15_spec_fits(p->geo.n, ld_y, F * p->geo.h + p->geo.n)) {
-        // N = 960 / 480 frame pairs (pairing off: the staged irfft + gather below)
-        e = crlot::launch_pair15_istft(p->geo, t, p->mask, d_spec, ld_spec, ld_frame, d_y, n_streams, F, ld_y, s);
-        return e == hipSuccess ? CRLOT_OK : hip_fail(e, "istft (frame pairs, N = 960 / 480) kernel launch");
-    }
-    if (p->pairing && crlot::pairn_spec_supported(p->geo.n, p->geo.h, p->geo.ring_len) && t.ptwn && t.ws && t.den &&
-        aligned4(d_y) && F * p->geo.h + p->geo.n < (int64_t(1) << 27)) {
-        // K_pairN's one-wave sizes as frame pairs (pairing off: the staged irfft + gather below)
-        e = crlot::launch_pairn_istft(p->geo, t, p->mask, d_spec, ld_spec, ld_frame, d_y, n_streams, F, ld_y, s);
-        return e == hipSuccess ? CRLOT_OK : hip_fail(e, "istft (frame pairs, K_pairN sizes) kernel launch");
-    }
-    if (istft_walk_ok(p, d_y, ld_y)) {
-        e = crlot::launch_istft(p->geo, t, p->mask, d_spec, ld_spec, ld_frame, d_y, n_streams, F, ld_y, s);
-        return e == hipSuccess ? CRLOT_OK : hip_fail(e, "istft kernel launch");
+    switch (istft_route(p, t, d_y, F, ld_y, n_streams).kind) {
+        case RouteKind::kPair:  // (pairing off: K_istft, bit-identical to irfft + gather)
+            e = crlot::launch_pair_istft(p->geo, t, p->mask, d_spec, ld_spec, ld_frame, d_y, n_streams, F, ld_y, s);
+            return e == hipSuccess ? CRLOT_OK : hip_fail(e, "istft (frame pairs) kernel launch");
+        case RouteKind::kPair15:  // (pairing off: the staged irfft + gather below)
+            e = crlot::launch_pair15_istft(p->geo, t, p->mask, d_spec, ld_spec, ld_frame, d_y, n_streams, F, ld_y, s);
+            return e == hipSuccess ? CRLOT_OK : hip_fail(e, "istft (frame pairs, N = 960 / 480) kernel launch");
+        case RouteKind::kPairN:  // (pairing off: the staged irfft + gather below)
+            e = crlot::launch_pairn_istft(p->geo, t, p->mask, d_spec, ld_spec, ld_frame, d_y, n_streams, F, ld_y, s);
+            return e == hipSuccess ? CRLOT_OK : hip_fail(e, "istft (frame pairs, K_pairN sizes) kernel launch");
+        case RouteKind::kWalk:
+            e = crlot::launch_istft(p->geo, t, p->mask, d_spec, ld_spec, ld_frame, d_y, n_streams, F, ld_y, s);
+            return e == hipSuccess ? CRLOT_OK : hip_fail(e, "istft kernel launch");
+        default: break;  // staged
     }
     const int n = p->geo.n, bins = n / 2 + 1;
     const int64_t rows = int64_t(n_streams) * F;
@@ -1146,39 +1233,28 @@ int istft_impl(crlot_plan* p, const float* d_spec, float* d_y, int32_t n_streams
 
 static int masked_roundtrip(crlot_plan* p, crlot::Scratch* sc, const float* d_x, float* d_y, int32_t n_streams,
                             int64_t T, int64_t ld_x, int64_t ld_y, int64_t F, hipStream_t s) {
-    const int64_t out_len = F * p->geo.h, lim = int64_t(1) << 29;
+    const int64_t out_len = F * p->geo.h;
     const crlot::DevTables t = tables(p);
-    if (p->pairing && crlot::pair_mask_supported(p->geo.n, p->geo.h) && crlot::pair_tables(p->geo, t) &&
-        p->geo.ring_len % p->geo.h == 0 && aligned4(d_x) && aligned4(d_y) && T < lim && out_len + 2 * p->geo.n < lim &&
-        int64_t(n_streams) * (T / p->geo.h + 1) < lim) {
-        // frame pairs (pairing off: the per-frame walk below, bit-identical to istft(stft))
-        const hipError_t e = crlot::launch_pair_masked(p->geo, t, p->mask, d_x, d_y, n_streams, T, ld_x, ld_y, F,
-                                                       out_len, s);
-        return e == hipSuccess ? CRLOT_OK : hip_fail(e, "masked frame-pair kernel launch");
-    }
-    if (p->pairing && crlot::pair15_spec_supported(p->geo.n, p->geo.h, p->geo.ring_len) && t.ptw && t.wa && t.ws &&
-        t.den && aligned4(d_x) && aligned4(d_y) && crlot::pair15_spec_fits(p->geo.n, ld_x, T) &&
-        crlot::pair15_spec_fits(p->geo.n, ld_y, out_len + p->geo.n)) {
-        // N = 960 / 480 frame pairs, one walk (pairing off: spectra through HBM below)
-        const hipError_t e = crlot::launch_pair15_masked(p->geo, t, p->mask, d_x, d_y, n_streams, T, ld_x, ld_y, F,
-                                                         out_len, s);
-        return e == hipSuccess ? CRLOT_OK : hip_fail(e, "masked frame-pair kernel launch (N = 960 / 480)");
-    }
-    if (p->pairing && crlot::pairn_spec_supported(p->geo.n, p->geo.h, p->geo.ring_len) && t.ptwn && t.wa && t.ws &&
-        t.den && aligned4(d_x) && aligned4(d_y) && T < (int64_t(1) << 27) && out_len + p->geo.n < (int64_t(1) << 27)) {
-        // K_pairN's one-wave sizes as frame pairs, one walk (pairing off: spectra through HBM below)
-        const hipError_t e = crlot::launch_pairn_masked(p->geo, t, p->mask, d_x, d_y, n_streams, T, ld_x, ld_y, F,
-                                                        out_len, s);
-        return e == hipSuccess ? CRLOT_OK : hip_fail(e, "masked frame-pair kernel launch (K_pairN sizes)");
-    }
-    if (masked_walk_ok(p, d_y, ld_y)) {
-        const hipError_t e = crlot::launch_roundtrip_masked(p->geo, tables(p), p->mask, d_x, d_y, n_streams, T, ld_x,
-                                                            ld_y, F, s);
-        return e == hipSuccess ? CRLOT_OK : hip_fail(e, "masked round trip kernel launch");
+    const Route r = masked_route(p, t, d_x, d_y, n_streams, T, ld_x, ld_y, F);
+    hipError_t e;
+    switch (r.kind) {
+        case RouteKind::kPair:  // (pairing off: the per-frame walk below, bit-identical to istft(stft))
+            e = crlot::launch_pair_masked(p->geo, t, p->mask, d_x, d_y, n_streams, T, ld_x, ld_y, F, out_len, s);
+            return e == hipSuccess ? CRLOT_OK : hip_fail(e, "masked frame-pair kernel launch");
+        case RouteKind::kPair15:  // one walk (pairing off: spectra through HBM below)
+            e = crlot::launch_pair15_masked(p->geo, t, p->mask, d_x, d_y, n_streams, T, ld_x, ld_y, F, out_len, s);
+            return e == hipSuccess ? CRLOT_OK : hip_fail(e, "masked frame-pair kernel launch (N = 960 / 480)");
+        case RouteKind::kPairN:  // one walk (pairing off: spectra through HBM below)
+            e = crlot::launch_pairn_masked(p->geo, t, p->mask, d_x, d_y, n_streams, T, ld_x, ld_y, F, out_len, s);
+            return e == hipSuccess ? CRLOT_OK : hip_fail(e, "masked frame-pair kernel launch (K_pairN sizes)");
+        case RouteKind::kWalk:
+            e = crlot::launch_roundtrip_masked(p->geo, t, p->mask, d_x, d_y, n_streams, T, ld_x, ld_y, F, s);
+            return e == hipSuccess ? CRLOT_OK : hip_fail(e, "masked round trip kernel launch");
+        default: break;  // staged
     }
     // through HBM: spectra (flat rows of N+2 floats), then the synthesis half
     const int64_t row = p->geo.n + 2, sp = int64_t(n_streams) * F * row;
-    int rc = ensure_workspace(sc, (sp + int64_t(n_streams) * F * p->geo.n) * int64_t(sizeof(float)));
+    int rc = ensure_workspace(sc, r.work_bytes);
     if (rc != CRLOT_OK) return rc;
     float* spec = sc->work;
     float* frames = sc->work + sp;
@@ -1224,8 +1300,8 @@ int crlot_stft(crlot_plan* p, const float* d_x, float* d_spec, int32_t n_streams
     crlot::Scratch* sc = scratch_slot(p, s);
     if (!sc) return fail(CRLOT_EHIP, "scratch slot");
     float* work = nullptr;
-    if (p->generic || !crlot::stft_supported(p->geo.n)) {
-        const int rc = ensure_workspace(sc, int64_t(n_streams) * F * p->geo.n * int64_t(sizeof(float)));
+    if (const Route r = stft_route(p, tables(p), d_x, T, ld_x, n_streams, F); r.kind == RouteKind::kStaged) {
+        const int rc = ensure_workspace(sc, r.work_bytes);
         if (rc != CRLOT_OK) return rc;
         work = sc->work;
     }
@@ -1253,12 +1329,11 @@ int crlot_istft_ola(crlot_plan* p, const float* d_spec, float* d_y, int32_t n_st
     if (!sc) return fail(CRLOT_EHIP, "scratch slot");
     float* specw = nullptr;
     float* frames = nullptr;
-    if (!istft_walk_ok(p, d_y, ld_y)) {
-        const int64_t sp = int64_t(n_streams) * F * row;
-        const int rc = ensure_workspace(sc, (sp + int64_t(n_streams) * F * p->geo.n) * int64_t(sizeof(float)));
+    if (const Route r = istft_route(p, tables(p), d_y, F, ld_y, n_streams); r.kind == RouteKind::kStaged) {
+        const int rc = ensure_workspace(sc, r.work_bytes);
         if (rc != CRLOT_OK) return rc;
         specw = sc->work;
-        frames = sc->work + sp;
+        frames = sc->work + int64_t(n_streams) * F * row;
     }
     return istft_impl(p, d_spec, d_y, n_streams, F, ld_spec, ld_frame, ld_y, specw, frames, s);
 }
@@ -1382,12 +1457,12 @@ int crlot_spectrogram(crlot_features* f, const float* d_x, float* d_out, int32_t
     fd.log = f->desc.log;
     fd.floor = f->desc.floor;
     fd.n_w = f->n_w;
-    const StftRoute route = stft_route(p, t, d_x, T, ld_x);
-    if (route == StftRoute::kPair && crlot::pair_feat_supported(p->geo.n, p->geo.h)) {
+    const RouteKind route = stft_route(p, t, d_x, T, ld_x, n_streams, F).kind;
+    if (route == RouteKind::kPair && crlot::pair_feat_supported(p->geo.n, p->geo.h)) {
         const hipError_t e = crlot::launch_pair_feat(p->geo, t, fd, d_x, n_streams, T, ld_x, F, s);
         return e == hipSuccess ? CRLOT_OK : hip_fail(e, "feature (frame pairs) kernel launch");
     }
-    if (route == StftRoute::kWalk && crlot::feat_walk_supported(p->geo.n)) {
+    if (route == RouteKind::kWalk && crlot::feat_walk_supported(p->geo.n)) {
         const hipError_t e = crlot::launch_feat(p->geo, t, fd, d_x, n_streams, T, ld_x, F, s);
         return e == hipSuccess ? CRLOT_OK : hip_fail(e, "feature kernel launch");
     }

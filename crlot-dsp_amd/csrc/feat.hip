@@ -318,24 +318,16 @@ hipError_t feat_e(FeatArgs& fa, hipStream_t stream) {
     // (+ the window, + the filterbank when it fits)
     const size_t lds = stft_lds<E>() + sizeof(float2) * Cfg<E>::P +
                        (feat_bank_in_lds(fa.f) ? sizeof(FeatBand) * fa.f.n_bands + sizeof(float) * fa.f.n_w : 0);
-    hipError_t e = set_lds(k_feat<E>, lds);
+    hipError_t e = set_lds(k_feat<E>, lds);  // (before the occupancy query, which needs the raised limit)
     if (e != hipSuccess) return e;
     pick_chunks(a.F, a.n_streams, resident_walkers(k_feat<E>, 64 * kW, lds, kW), 1, a.n_chunks, a.M);
-    note_chunks(a.n_chunks);
     const int64_t grid = (int64_t(a.n_streams) * a.n_chunks + kW - 1) / kW;
-    note_launch(CRLOT_K_FEAT, grid);
-    hipLaunchKernelGGL(k_feat<E>, dim3(unsigned(grid)), dim3(64 * kW), lds, stream, fa);
-    return hipGetLastError();
+    return launch_kernel_plain(k_feat<E>, CRLOT_K_FEAT, dim3(unsigned(grid)), dim3(64 * kW), lds, stream, fa);
 }
 
 template <typename K>
 hipError_t pair_feat_launch(K kernel, const PairFeatArgs& a, int64_t walkers, hipStream_t stream) {
-    hipError_t e = set_lds(kernel, SpecLds::bytes);
-    if (e != hipSuccess) return e;
-    const int64_t grid = (walkers + kSW - 1) / kSW;
-    note_launch(CRLOT_K_PAIR_FEAT, grid);
-    hipLaunchKernelGGL(kernel, dim3(unsigned(grid)), dim3(64 * kSW), SpecLds::bytes, stream, a);
-    return hipGetLastError();
+    return launch_kernel(kernel, CRLOT_K_PAIR_FEAT, (walkers + kSW - 1) / kSW, 64 * kSW, SpecLds::bytes, stream, a);
 }
 
 int pair_feat_walkers_per_cu() {
@@ -376,24 +368,11 @@ hipError_t launch_pair_feat(const Geometry& g, const DevTables& t, const FeatDev
     if (!pair_feat_supported(g.n, g.h) || F <= 0 || n_streams <= 0 || F > INT32_MAX || !pair_tables(g, t))
         return hipErrorInvalidValue;
     PairFeatArgs a{};
-    a.f.t = t;
-    a.f.x = x;
-    a.f.ld_x = ld_x;
-    a.f.T = int(T);
-    a.f.n_streams = n_streams;
-    a.f.F = int(F);
-    a.f.pad = g.pad;
-    a.f.pad_mode = g.pad_mode;
+    a.f = pair_stft_args(g, t, x, n_streams, T, ld_x, F, nullptr, 0, 0).f;
     a.fd = f;
-    const int64_t S = std::max(1, n_streams), resident = int64_t(cus()) * pair_feat_walkers_per_cu();
-    int64_t n = std::max<int64_t>((F + 127) / 128, (2 * resident + S - 1) / S);
-    n = std::max<int64_t>(1, std::min<int64_t>(n, (F + 1) / 2));  // (down to one pair per walk: small batches)
-    if (const int64_t c = chunks_or(0, F); c > 0) n = std::min(c, F);
-    int64_t m = (F + n - 1) / n;
-    m += m & 1;
-    a.f.M = int(m);
-    a.f.n_chunks = int((F + m - 1) / m);
-    note_chunks(a.f.n_chunks);
+    // (down to one pair per walk: small batches)
+    choose_chunks_two_rounds(F, n_streams, int64_t(device_cus()) * pair_feat_walkers_per_cu(), (F + 1) / 2,
+                             kChunkFill128 | kChunkEven, a.f.n_chunks, a.f.M);
     const int64_t walkers = int64_t(n_streams) * a.f.n_chunks;
     switch (g.h) {
         case 128: return pair_feat_launch(k_pair_feat<2>, a, walkers, stream);
@@ -409,12 +388,8 @@ hipError_t launch_feat_step(const FeatDev& f, const float* spec, int64_t ld_spec
     if (rows <= 0 || grid > INT32_MAX || bins <= 0) return hipErrorInvalidValue;
     const int vstride = f.n_bands ? (bins + 3) & ~3 : 0;
     const size_t lds = sizeof(float) * size_t(vstride) * kW;
-    hipError_t e = set_lds(k_feat_step, lds);
-    if (e != hipSuccess) return e;
-    note_launch(CRLOT_K_FEAT_STEP, grid);
-    hipLaunchKernelGGL(k_feat_step, dim3(unsigned(grid)), dim3(64 * kW), lds, stream, spec, ld_spec, ld_row, F, rows,
-                       bins, vstride, f);
-    return hipGetLastError();
+    return fk::launch_kernel(k_feat_step, CRLOT_K_FEAT_STEP, grid, 64 * kW, lds, stream, spec, ld_spec, ld_row, F, rows,
+                             bins, vstride, f);
 }
 
 }  // namespace crlot

@@ -1,5 +1,7 @@
-// fused_common.h -- device and host pieces shared by the fused walker kernels
-// (kernels.hip: K_fused*, K_pair512/2k/4k, K_fused_wg; pair1k.hip: K_pair).
+// fused_common.h -- device pieces and argument structs shared by the fused walker
+// kernels (kernels.hip: K_fused*, K_pair512/2k/4k, K_fused_wg; pair1k.hip: K_pair).
+// The host launch layer (argument fill, launch epilogue, chunk policies, CU count)
+// lives in launch_common.h / launch.cpp.
 #pragma once
 
 #include <cstdint>

@@ -6,6 +6,8 @@
 //   ring:    OLAAccumulator::calculate_ring_size (OLAAccumulator.cc:249-258)
 //   norm:    OLAAccumulator::initialize_normalization (OLAAccumulator.cc:260-288)
 //            + dsp::ola::build_norm_linear (norm_builder.cc:8-52)
+// and the product's own twiddle tables that need no device header
+// (build_pair_wg_twiddles).
 //
 // Bit-exactness against the reference's compiled sources is checked by
 // tests/test_host_abi.py (test_window_tables_bit_exact_vs_reference,
@@ -18,6 +20,7 @@
 
 #include "batch.h"
 #include "crlot_dsp.h"
+#include "kernels.h"
 
 namespace {
 
@@ -52,6 +55,27 @@ void normalize(float* w, int64_t n, int32_t norm) {
 }
 
 }  // namespace
+
+namespace crlot {
+// The workgroup pair transforms' tables (fft_pair512.h, fft_pair2k.h, fft_pair4k.h):
+// W_n^{l k1} for k1 < n / lanes and the lanes l, then W_lanes^{x k2} for k2 < n / lanes
+// and x < group, float pairs.
+std::vector<float> build_pair_wg_twiddles(int n, int lanes, int group) {
+    std::vector<float> t;
+    auto put = [&](double ph) {
+        t.push_back(float(std::cos(ph)));
+        t.push_back(float(std::sin(ph)));
+    };
+    for (int k1 = 1; k1 < n / lanes; ++k1)
+        for (int l = 0; l < lanes; ++l) put(-2.0 * M_PI * double(l * k1) / double(n));
+    for (int k2 = 1; k2 < n / lanes; ++k2)
+        for (int x = 0; x < group; ++x) put(-2.0 * M_PI * double(x * k2) / double(lanes));
+    return t;
+}
+std::vector<float> build_pair512_twiddles() { return build_pair_wg_twiddles(512, 64, 8); }
+std::vector<float> build_pair2k_twiddles() { return build_pair_wg_twiddles(2048, 128, 8); }
+std::vector<float> build_pair4k_twiddles() { return build_pair_wg_twiddles(4096, 256, 16); }
+}  // namespace crlot
 
 extern "C" int crlot_window_table(int32_t type, int64_t n, int32_t periodic, int32_t norm,
                                   float* out) {

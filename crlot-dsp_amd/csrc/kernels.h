@@ -1,4 +1,5 @@
-// kernels.h -- host-side launch interface of the HIP kernels (internal).
+// kernels.h -- host-side launch interface of the HIP kernels (internal).  The
+// launchers are written on the host launch layer of launch_common.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -86,10 +87,13 @@ int64_t chunks_or(int64_t dflt, int64_t max_chunks);
 
 // Tables of the frame-pair transform (fft_pair.h) for N = 1024, float pairs.
 std::vector<float> build_pair_twiddles();
-// ... and of the 4096- and 512-point ones (fft_pair4k.h, fft_pair512.h).
+// ... and of the workgroup pair transforms: n points on `lanes` lanes in groups of
+// `group` (build_pair_wg_twiddles), at the 4096-, 512- and 2048-point walkers'
+// constants (fft_pair4k.h, fft_pair512.h, fft_pair2k.h; N = 2048's stored in DevTables::ptw4)
+std::vector<float> build_pair_wg_twiddles(int n, int lanes, int group);
 std::vector<float> build_pair4k_twiddles();
 std::vector<float> build_pair512_twiddles();
-std::vector<float> build_pair2k_twiddles();  // fft_pair2k.h (N = 2048; stored in DevTables::ptw4)
+std::vector<float> build_pair2k_twiddles();
 
 // Per-pass Stockham twiddles for an N-point real frame (P = N/2 complex points),
 // laid out as the device reads them (fft_wave.h twiddle_table_size), computed in
@@ -112,6 +116,8 @@ struct Geometry {
 // Fused fast path: N in {256..2048}, H % 128 == 0, N % H == 0, ring_len % H == 0,
 // 8-byte aligned streams.  Returns false if this shape has no instantiation.
 bool fused_supported(int n, int h);
+// the tables of K_pair (N = 1024 frame pairs: 4-byte aligned rows) are there
+bool pair1k_plan(const Geometry& g, const DevTables& t);
 hipError_t launch_fused(const Geometry& g, const DevTables& t, const float* x, float* y,
                         int n_streams, int64_t T, int64_t ld_x, int64_t ld_y, int64_t F,
                         int64_t out_len, hipStream_t stream);
@@ -411,11 +417,11 @@ hipError_t launch_istft(const Geometry& g, const DevTables& t, const SpecMask& m
 hipError_t launch_roundtrip_masked(const Geometry& g, const DevTables& t, const SpecMask& m, const float* x,
                                    float* y, int n_streams, int64_t T, int64_t ld_x, int64_t ld_y, int64_t F,
                                    hipStream_t s);
-// ... as frame pairs (K_pair_mask, pair_mask.hip: N = 1024, H = 128 / 256 / 512, the
-// pair tables; equal to the per-frame walk within float32 rounding)
+// ... as frame pairs (K_pair_mask; equal to the per-frame walk within float32 rounding) at
+// N = 1024 (H 128, 256, 512) and 512 (H 128, 256) on one wave (pair_mask.hip), N = 2048
+// (H 256, 512, 1024) and 4096 (H 512, 1024, 2048) on one workgroup (pair_wg_spec.hip), the pair tables
 bool pair_mask_supported(int n, int h);
-bool pair_spec_supported(int n, int h);  // K_pair_stft / K_pair_istft: N = 1024 (H 128-512), 512 (H 128, 256),
-                                         // 2048 (H 256, 512), 4096 (H 512, 1024)
+bool pair_spec_supported(int n, int h);  // K_pair_stft / K_pair_istft: the same shapes
 bool pair_tables(const Geometry& g, const DevTables& t);  // the tables those kernels read are there
 // ... and at N = 960 / 480 (K_pair15's transforms, any hop >= 32 with ring_len % H == 0; pair15_spec.hip)
 bool pair15_spec_supported(int n, int h, int ring_len);
@@ -440,8 +446,8 @@ hipError_t launch_pair15_istft(const Geometry& g, const DevTables& t, const Spec
 hipError_t launch_pair15_masked(const Geometry& g, const DevTables& t, const SpecMask& m, const float* x, float* y,
                                 int n_streams, int64_t T, int64_t ld_x, int64_t ld_y, int64_t F, int64_t out_len,
                                 hipStream_t stream);
-// crlot_stft / crlot_istft_ola as frame pairs (K_pair_stft / K_pair_istft, pair_stft.hip:
-// N = 1024, H = 128 / 256 / 512, the pair tables; within float32 rounding of the per-frame kernels)
+// crlot_stft / crlot_istft_ola as frame pairs (K_pair_stft / K_pair_istft: pair_spec_supported's
+// shapes, the pair tables; within float32 rounding of the per-frame kernels)
 hipError_t launch_pair_stft(const Geometry& g, const DevTables& t, const float* x, int n_streams, int64_t T,
                             int64_t ld_x, int64_t F, float* spec, int64_t ld_spec, int64_t ld_frame, hipStream_t s);
 hipError_t launch_pair_istft(const Geometry& g, const DevTables& t, const SpecMask& m, const float* spec,

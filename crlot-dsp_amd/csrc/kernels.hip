@@ -20,6 +20,9 @@
 // update fma(fma(src, w, 0), g, dst) (kernels.cc:24-28) and the IEEE division
 // acc / max(norm, eps) (kernels.cc:30-36).  Built with -ffp-contract=off and
 // the default correctly-rounded f32 division; subnormals are preserved.
+//
+// The `dispatch` half below is written on the host launch layer (launch_common.h,
+// launch.cpp): argument fill, launch epilogue, chunk policies, CU count.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -31,7 +34,7 @@
 #include "fft_pair512.h"
 #include "fft_pair2k.h"
 #include "fft_wave.h"
-#include "fused_common.h"
+#include "launch_common.h"
 #include "kernels.h"
 #include "stream_common.h"
 
@@ -1636,6 +1639,8 @@ __global__ __launch_bounds__(kBlock) void k_stream_hop(const StreamArgs a) {
 }
 
 // ------------------------------------------------------------------ dispatch
+// (the compute-unit count, the kernel-argument fill, the launch epilogue and the
+// chunk policies: the host launch layer, launch_common.h / launch.cpp)
 template <int E>
 inline size_t lds_bytes_full() {
     return Lds<E>::bytes;
@@ -1680,21 +1685,12 @@ hipError_t fused_es(const FusedArgs& a, int64_t grid, hipStream_t stream) {
     if (fused2_used(E, S, fast)) {
         auto k2 = a.t.gain ? k_stft_ola_fused2<E, S, NB, true> : k_stft_ola_fused2<E, S, NB, false>;
         const size_t lds2 = Lds<E>::bytes + sizeof(cf) * kWaves * 64 * E;
-        hipError_t e2 = set_lds(k2, lds2);
-        if (e2 != hipSuccess) return e2;
-        note_launch(CRLOT_K_FUSED2, grid);
-        hipLaunchKernelGGL(k2, dim3(unsigned(grid)), dim3(kBlock), lds2, stream, a);
-        return hipGetLastError();
+        return launch_kernel(k2, CRLOT_K_FUSED2, grid, kBlock, lds2, stream, a);
     }
 #endif
     auto k = a.t.gain ? (fast ? k_stft_ola_fused<E, S, NB, true, true> : k_stft_ola_fused<E, S, NB, true, false>)
                       : (fast ? k_stft_ola_fused<E, S, NB, false, true> : k_stft_ola_fused<E, S, NB, false, false>);
-    const size_t lds = Lds<E>::bytes;
-    hipError_t e = set_lds(k, lds);
-    if (e != hipSuccess) return e;
-    note_launch(CRLOT_K_FUSED, grid);
-    hipLaunchKernelGGL(k, dim3(unsigned(grid)), dim3(kBlock), lds, stream, a);
-    return hipGetLastError();
+    return launch_kernel(k, CRLOT_K_FUSED, grid, kBlock, Lds<E>::bytes, stream, a);
 }
 
 // CRLOT_PAIR4K_NOHOT=1 (A/B, N = 4096, 2048 and 512): the two-regime walker alone over every chunk.
@@ -1726,21 +1722,17 @@ hipError_t pair512_sh(const FusedArgs& a, int64_t waves, hipStream_t stream) {
     constexpr int NB = 8 / SH;
     auto k = a.t.gain ? k_stft_ola_pair512<SH, NB, true> : k_stft_ola_pair512<SH, NB, false>;
     const size_t lds = sizeof(cf) * dev::kP512Buf * kP512Waves;
-    hipError_t e = set_lds(k, lds);
-    if (e != hipSuccess) return e;
     const int64_t grid = (waves + kP512Waves - 1) / kP512Waves;
     if (!a.t.pflags || a.t.pflags_len < waves) return hipErrorInvalidValue;
     FusedArgs b = a;
     // the paired-only hot walker (H = 128, 256), then this two-regime walker over
     // the chunks it flagged; a gain or reflect/edge padding: the latter alone
     if ((SH == 2 || SH == 4) && !a.t.gain && a.pad_mode == 0 && !pair4k_hot_disabled() && a.t.hot) {
-        if ((e = launch_pair512_hot(SH, a, waves, kP512Waves, stream)) != hipSuccess) return e;
+        if (hipError_t e = launch_pair512_hot(SH, a, waves, kP512Waves, stream); e != hipSuccess) return e;
     } else {
         b.fix_all = 1;
     }
-    note_launch(CRLOT_K_PAIR512, grid);
-    hipLaunchKernelGGL(k, dim3(unsigned(grid)), dim3(64 * kP512Waves), lds, stream, b);
-    return hipGetLastError();
+    return launch_kernel(k, CRLOT_K_PAIR512, grid, 64 * kP512Waves, lds, stream, b);
 }
 hipError_t launch_pair512(int sh, const FusedArgs& a, int64_t waves, hipStream_t stream) {
     switch (sh) {
@@ -1756,33 +1748,12 @@ template <int SH>
 hipError_t pair2k_sh(const FusedArgs& a, int64_t grid, hipStream_t stream) {
     constexpr int NB = 16 / SH;
     auto k = a.t.gain ? k_stft_ola_pair2k<SH, NB, true> : k_stft_ola_pair2k<SH, NB, false>;
-    hipError_t e = set_lds(k, kPair2kLds);
-    if (e != hipSuccess) return e;
-    note_launch(CRLOT_K_PAIR2K, grid);
-    hipLaunchKernelGGL(k, dim3(unsigned(grid)), dim3(128), kPair2kLds, stream, a);
-    return hipGetLastError();
+    return launch_kernel(k, CRLOT_K_PAIR2K, grid, 128, kPair2kLds, stream, a);
 }
-void choose_chunks_rounds(int64_t F, int n_streams, int halo, int resident, int& n_chunks, int& m);
-// The plan's chunk knob (crlot_plan_set_chunks, via the call's LaunchCtl)
-// replaces the chooser's chunking: min(knob, F) chunks per stream.
-void chunk_override(int64_t F, FusedArgs& a) {
-    const int64_t n = chunks_or(0, F);
-    if (n <= 0) return;
-    a.M = int((F + n - 1) / n);
-    a.n_chunks = int((F + a.M - 1) / a.M);
-}
-int fused_resident_waves();
 hipError_t launch_pair2k(const Geometry& g, FusedArgs a, int64_t F, int n_streams, hipStream_t stream) {
     const bool hot = g.h == 512 && !a.t.gain && g.pad_mode == 0 && !pair4k_hot_disabled() && a.t.hot;
     const bool hot3 = hot && pair4k_hot3();  // six two-wave workgroups per CU, else four
-    choose_chunks_rounds(F, n_streams, g.n / g.h + 1, fused_resident_waves() / 16 * (hot3 ? 6 : 4), a.n_chunks, a.M);
-    chunk_override(F, a);
-    note_chunks(a.n_chunks);
-    a.ring_blocks = g.ring_len / g.h;
-    a.pad = g.pad;
-    a.pad_mode = g.pad_mode;
-    a.inv_n = g.inv_n;
-    a.gain = g.gain;
+    choose_chunks_rounds(F, n_streams, g.n / g.h + 1, device_cus() * (hot3 ? 6 : 4), a.n_chunks, a.M);
     const int64_t grid = int64_t(n_streams) * a.n_chunks;
     if (!a.t.pflags || a.t.pflags_len < grid) return hipErrorInvalidValue;
     // the paired-only hot walker where it holds its registers (H = 512), then the
@@ -1821,61 +1792,6 @@ hipError_t fused_e(int s, const FusedArgs& a, int64_t grid, hipStream_t stream) 
     return hipErrorInvalidValue;
 }
 
-// Waves of K_fused the device holds at once: 4 per SIMD (<= 128 VGPRs), 4 SIMDs
-// per CU.
-int fused_resident_waves() {
-    static const int v = [] {
-        int dev = 0, cus = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-            cus <= 0)
-            cus = 256;
-        return 16 * cus;
-    }();
-    return v;
-}
-
-// Split each stream's F frames into n chunks (one wave each; NB-1 halo frames
-// recomputed per chunk).  Measured on MI355X (scripts/sweep_chunks.sh): ~128-frame
-// chunks are right while the grid is several resident rounds deep (headline:
-// flat for 12..24 chunks), but a small batch must still fill the device -- at
-// least one resident round of waves, two when chunks stay >= 48 frames (config 2:
-// +5 %, config 4 batched: +20 % over fixed 128-frame chunks).
-void choose_chunks(int64_t F, int n_streams, int nb, int resident, int& n_chunks, int& m) {
-    (void)nb;
-    const int64_t S = std::max(1, n_streams);
-    int64_t n = (F + 127) / 128;
-    n = std::max<int64_t>(n, (resident + S - 1) / S);
-    const int64_t two = (2 * resident + S - 1) / S;
-    if (two > n && F / two >= 48) n = two;
-    n = std::max<int64_t>(1, std::min<int64_t>(n, std::max<int64_t>(1, F / 32)));
-    m = int((F + n - 1) / n);
-    n_chunks = int((F + m - 1) / m);
-}
-
-// K_pair*: whole resident rounds.  A pair kernel's workgroup only frees its
-// slots when all of its waves finish, so a grid that ends in a partial round
-// idles the device for a whole chunk's time (headline, 16 waves/CU: 15 chunks
-// = 3.75 rounds 219k Msamples/s, 8 chunks = 2 rounds 232k).  Among chunk counts
-// with chunks of >= 48 frames, the fewest (rounds + 0.1) x (frames + halo + 10)
-// per wave: the 0.1 charges a single long round for its tail, the 10 a wave's
-// start-up (tables, first hops) (measured: headline 6 chunks = 2 rounds best,
-// 9-15 within 1-3 %; config-4 shape 64 chunks = one round best).
-void choose_chunks_rounds(int64_t F, int n_streams, int halo, int resident, int& n_chunks, int& m) {
-    const int64_t S = std::max(1, n_streams), R = std::max(1, resident);
-    const int64_t hi = std::max<int64_t>(1, F / 48);
-    const int64_t lo = std::min(hi, (F + 511) / 512);
-    int64_t best_n = lo;
-    double best_cost = 1e300;
-    for (int64_t n = lo; n <= hi; ++n) {
-        const int64_t mm = (F + n - 1) / n, nc = (F + mm - 1) / mm;
-        const double cost = (double((S * nc + R - 1) / R) + 0.1) * double(mm + halo + 10);
-        if (cost < best_cost) best_cost = cost, best_n = n;
-    }
-    m = int((F + best_n - 1) / best_n);
-    n_chunks = int((F + m - 1) / m);
-}
-
 // frames per workgroup walk (halo NB-1 frames recomputed); CRLOT_WG_CHUNK overrides
 int wg_chunk_target() {
     static const int v = [] {
@@ -1893,6 +1809,10 @@ bool pair_mask_supported(int n, int h) {
            fk::pair_wg_supported(n, h);
 }
 bool pair_spec_supported(int n, int h) { return pair_mask_supported(n, h); }
+// the plan runs K_pair (N = 1024 frame pairs) once a call brings the walkers' flags
+bool pair1k_plan(const Geometry& g, const DevTables& t) {
+    return g.n == 1024 && t.ptw && t.pden && t.wsn && t.rden;
+}
 // the frame-pair kernels' tables (N = 2048 / 4096 keep theirs in ptw4 / pden4)
 bool pair_tables(const Geometry& g, const DevTables& t) {
     return (g.n >= 2048 ? (t.ptw4 && t.pden4) : (t.ptw && t.pden)) && t.wa && t.wsn && t.rden;
@@ -1905,35 +1825,9 @@ hipError_t launch_pair_masked(const Geometry& g, const DevTables& t, const SpecM
     if (!pair_mask_supported(g.n, g.h) || F <= 0 || n_streams <= 0 || !m.p || !pair_tables(g, t) ||
         g.ring_len % g.h != 0)
         return hipErrorInvalidValue;
-    FusedArgs a;
-    a.t = t;
-    a.x = x;
-    a.y = y;
-    a.ld_x = ld_x;
-    a.ld_y = ld_y;
-    a.T = int(T);
-    a.out_len = int(out_len);
-    a.n_streams = n_streams;
-    a.F = int(F);
-    const int resident = fused_resident_waves() / 16 * fk::pair_mask_walkers_per_cu(g.n);
-    choose_chunks_rounds(F, n_streams, g.n / g.h + 1, resident, a.n_chunks, a.M);
-    // a batch below one resident round (one window of a few streams: the per-call
-    // latency case) walks chunks of >= 8 frames instead, as many as fit the round
-    const int64_t S = std::max(1, n_streams);
-    if (S * a.n_chunks < resident) {
-        const int64_t n = std::min<int64_t>(F / 8, (resident + S - 1) / S);
-        if (n > a.n_chunks) {
-            a.M = int((F + n - 1) / n);
-            a.n_chunks = int((F + a.M - 1) / a.M);
-        }
-    }
-    chunk_override(F, a);
-    note_chunks(a.n_chunks);
-    a.ring_blocks = g.ring_len / g.h;
-    a.pad = g.pad;
-    a.pad_mode = g.pad_mode;
-    a.inv_n = g.inv_n;
-    a.gain = g.gain;
+    FusedArgs a = fused_args(g, t, x, y, n_streams, T, ld_x, ld_y, F, out_len);
+    const int resident = device_cus() * fk::pair_mask_walkers_per_cu(g.n);
+    choose_chunks_rounds(F, n_streams, g.n / g.h + 1, resident, a.n_chunks, a.M, /*small_batches=*/true);
     return fk::launch_pair_mask(g.n, g.h, a, m, int64_t(n_streams) * a.n_chunks, stream);
 }
 
@@ -1943,27 +1837,10 @@ hipError_t launch_pair_stft(const Geometry& g, const DevTables& t, const float* 
                             int64_t ld_x, int64_t F, float* spec, int64_t ld_spec, int64_t ld_frame,
                             hipStream_t stream) {
     if (!pair_spec_supported(g.n, g.h) || F <= 0 || n_streams <= 0 || !pair_tables(g, t)) return hipErrorInvalidValue;
-    fk::PairSpecArgs a{};
-    a.f.t = t;
-    a.f.x = x;
-    a.f.ld_x = ld_x;
-    a.f.T = int(T);
-    a.f.n_streams = n_streams;
-    a.f.F = int(F);
-    a.f.pad = g.pad;
-    a.f.pad_mode = g.pad_mode;
-    a.spec = spec;
-    a.ld_spec = ld_spec;
-    a.ld_frame = ld_frame;
-    const int64_t S = std::max(1, n_streams), resident = fused_resident_waves() / 16 * fk::pair_spec_walkers_per_cu(g.n);
-    int64_t n = std::max<int64_t>((F + 127) / 128, (2 * resident + S - 1) / S);
-    n = std::max<int64_t>(1, std::min<int64_t>(n, (F + 1) / 2));  // (down to one pair per walk: small batches)
-    if (const int64_t c = chunks_or(0, F); c > 0) n = std::min(c, F);
-    int64_t m = (F + n - 1) / n;
-    m += m & 1;
-    a.f.M = int(m);
-    a.f.n_chunks = int((F + m - 1) / m);
-    note_chunks(a.f.n_chunks);
+    fk::PairSpecArgs a = pair_stft_args(g, t, x, n_streams, T, ld_x, F, spec, ld_spec, ld_frame);
+    // (down to one pair per walk: small batches)
+    choose_chunks_two_rounds(F, n_streams, int64_t(device_cus()) * fk::pair_spec_walkers_per_cu(g.n), (F + 1) / 2,
+                             kChunkFill128 | kChunkEven, a.f.n_chunks, a.f.M);
     return fk::launch_pair_stft(g.n, g.h, a, int64_t(n_streams) * a.f.n_chunks, stream);
 }
 
@@ -1973,86 +1850,14 @@ hipError_t launch_pair_istft(const Geometry& g, const DevTables& t, const SpecMa
                              hipStream_t stream) {
     if (!pair_spec_supported(g.n, g.h) || F <= 0 || n_streams <= 0 || !pair_tables(g, t) || g.ring_len % g.h != 0)
         return hipErrorInvalidValue;
-    fk::PairSpecArgs a{};
-    a.f.t = t;
-    a.f.y = y;
-    a.f.ld_y = ld_y;
-    a.f.out_len = int(F * g.h);
-    a.f.n_streams = n_streams;
-    a.f.F = int(F);
-    a.f.ring_blocks = g.ring_len / g.h;
-    a.f.inv_n = g.inv_n;
-    a.f.gain = g.gain;
-    a.sin = spec;
-    a.ld_spec = ld_spec;
-    a.ld_frame = ld_frame;
-    a.mask = m;
-    const int resident = fused_resident_waves() / 16 * fk::pair_spec_walkers_per_cu(g.n);
-    choose_chunks_rounds(F, n_streams, g.n / g.h + 1, resident, a.f.n_chunks, a.f.M);
-    const int64_t S = std::max(1, n_streams);
-    if (S * a.f.n_chunks < resident) {  // (small batches: chunks of >= 8 frames, as the mask walker)
-        const int64_t n = std::min<int64_t>(F / 8, (resident + S - 1) / S);
-        if (n > a.f.n_chunks) {
-            a.f.M = int((F + n - 1) / n);
-            a.f.n_chunks = int((F + a.f.M - 1) / a.f.M);
-        }
-    }
-    chunk_override(F, a.f);
-    note_chunks(a.f.n_chunks);
+    fk::PairSpecArgs a = pair_istft_args(g, t, m, spec, ld_spec, ld_frame, y, n_streams, F, ld_y);
+    const int resident = device_cus() * fk::pair_spec_walkers_per_cu(g.n);
+    choose_chunks_rounds(F, n_streams, g.n / g.h + 1, resident, a.f.n_chunks, a.f.M, /*small_batches=*/true);
     return fk::launch_pair_istft(g.n, g.h, a, int64_t(n_streams) * a.f.n_chunks, stream);
 }
 
-std::vector<float> build_pair512_twiddles() {
-    std::vector<float> t;
-    for (int k1 = 1; k1 < 8; ++k1)
-        for (int l = 0; l < 64; ++l) {
-            const double ph = -2.0 * M_PI * double(l * k1) / 512.0;
-            t.push_back(float(std::cos(ph)));
-            t.push_back(float(std::sin(ph)));
-        }
-    for (int k2 = 1; k2 < 8; ++k2)
-        for (int x = 0; x < 8; ++x) {
-            const double ph = -2.0 * M_PI * double(x * k2) / 64.0;
-            t.push_back(float(std::cos(ph)));
-            t.push_back(float(std::sin(ph)));
-        }
-    return t;
-}
-
-std::vector<float> build_pair2k_twiddles() {
-    std::vector<float> t;
-    for (int k1 = 1; k1 < 16; ++k1)
-        for (int l = 0; l < 128; ++l) {
-            const double ph = -2.0 * M_PI * double(l * k1) / 2048.0;
-            t.push_back(float(std::cos(ph)));
-            t.push_back(float(std::sin(ph)));
-        }
-    for (int k2 = 1; k2 < 16; ++k2)
-        for (int x = 0; x < 8; ++x) {
-            const double ph = -2.0 * M_PI * double(x * k2) / 128.0;
-            t.push_back(float(std::cos(ph)));
-            t.push_back(float(std::sin(ph)));
-        }
-    return t;
-}
-
-std::vector<float> build_pair4k_twiddles() {
-    std::vector<float> t;
-    for (int k1 = 1; k1 < 16; ++k1)
-        for (int l = 0; l < 256; ++l) {
-            const double ph = -2.0 * M_PI * double(l * k1) / 4096.0;
-            t.push_back(float(std::cos(ph)));
-            t.push_back(float(std::sin(ph)));
-        }
-    for (int k2 = 1; k2 < 16; ++k2)
-        for (int x = 0; x < 16; ++x) {
-            const double ph = -2.0 * M_PI * double(x * k2) / 256.0;
-            t.push_back(float(std::cos(ph)));
-            t.push_back(float(std::sin(ph)));
-        }
-    return t;
-}
-
+// (build_pair512 / 2k / 4k_twiddles: host_tables.cpp; the builders below read the
+// device headers' constexpr helpers and stay with them)
 std::vector<float> build_pass_twiddles(int n) {
     const int p = n / 2, e = p / 64;
     std::vector<float> t;
@@ -2084,31 +1889,19 @@ hipError_t launch_fused(const Geometry& g, const DevTables& t, const float* x, f
                         int n_streams, int64_t T, int64_t ld_x, int64_t ld_y, int64_t F,
                         int64_t out_len, hipStream_t stream) {
     if (!fused_supported(g.n, g.h) || F <= 0 || n_streams <= 0) return hipErrorInvalidValue;
-    FusedArgs a;
-    a.t = t;
-    a.x = x;
-    a.y = y;
-    a.ld_x = ld_x;
-    a.ld_y = ld_y;
-    a.T = int(T);
-    a.out_len = int(out_len);
-    a.n_streams = n_streams;
-    a.F = int(F);
+    FusedArgs a = fused_args(g, t, x, y, n_streams, T, ld_x, ld_y, F, out_len);
     const int e = e_of(g.n);
     const bool fast = t.wsn && t.rden;
 #ifdef CRLOT_NO_PAIR  // A/B builds: per-frame kernels only
     const bool use_pair = false;
 #else
-    const bool use_pair = g.n == 1024 && t.ptw && t.pden && t.pflags && fast;
+    const bool use_pair = pair1k_plan(g, t) && t.pflags;
 #endif
     const bool use_pair512 = g.n == 512 && t.ptw && t.pden && fast && g.h >= 128;
     if (g.n == 2048 && t.ptw4 && t.pden4 && fast && (g.h == 256 || g.h == 512 || g.h == 1024))
         return launch_pair2k(g, a, F, n_streams, stream);
 #ifdef CRLOT_OLD_CHUNKS  // A/B builds: fixed ~128-frame chunks
-    const int target = 128;
-    a.n_chunks = int((F + target - 1) / target);
-    a.M = int((F + a.n_chunks - 1) / a.n_chunks);
-    a.n_chunks = int((F + a.M - 1) / a.M);
+    choose_chunks_fixed(F, 128, a.n_chunks, a.M);
 #else
     // K_fused and K_pair keep 4 waves/SIMD resident, K_fused2 3
     const bool pair = !use_pair && fused2_used(e, g.h / 128, fast);
@@ -2118,15 +1911,8 @@ hipError_t launch_fused(const Geometry& g, const DevTables& t, const float* x, f
         choose_chunks_rounds(F, n_streams, g.n / g.h + 1, use_pair512 ? fused_resident_waves() : resident,
                              a.n_chunks, a.M);
     else
-        choose_chunks(F, n_streams, g.n / g.h, resident, a.n_chunks, a.M);
-    chunk_override(F, a);
+        choose_chunks(F, n_streams, resident, a.n_chunks, a.M);
 #endif
-    note_chunks(a.n_chunks);
-    a.ring_blocks = g.ring_len / g.h;
-    a.pad = g.pad;
-    a.pad_mode = g.pad_mode;
-    a.inv_n = g.inv_n;
-    a.gain = g.gain;
     const int64_t waves = int64_t(n_streams) * a.n_chunks;
     if (use_pair) return launch_pair(g.h / 64, a, waves, stream);
     if (use_pair512) return launch_pair512(g.h / 64, a, waves, stream);
@@ -2148,34 +1934,15 @@ hipError_t launch_fused(const Geometry& g, const DevTables& t, const float* x, f
 hipError_t launch_pair_interleaved(const Geometry& g, const DevTables& t, const float* x, float* y, int n_groups,
                                    int channels, int64_t T, int64_t ld_x, int64_t ld_y, int64_t F,
                                    int64_t out_len, hipStream_t stream) {
-    const bool fast = t.wsn && t.rden;
-    if (!(g.n == 1024 && t.ptw && t.pden && t.pflags && fast && g.pad_mode == 0 && fused_supported(g.n, g.h) &&
-          g.h <= 512))
+    if (!(pair1k_plan(g, t) && t.pflags && g.pad_mode == 0 && fused_supported(g.n, g.h) && g.h <= 512))
         return hipErrorNotSupported;
     const int64_t S = int64_t(n_groups) * channels;
     if (F <= 0 || n_groups <= 0 || channels < 1 || S > INT32_MAX || (T + 2 * g.n) * channels >= (int64_t(1) << 29) ||
         (out_len + 2 * g.n) * channels >= (int64_t(1) << 29))
         return hipErrorInvalidValue;
-    FusedArgs a;
-    a.t = t;
-    a.x = x;
-    a.y = y;
-    a.ld_x = ld_x;
-    a.ld_y = ld_y;
-    a.T = int(T);
-    a.out_len = int(out_len);
-    a.n_streams = int(S);
-    a.F = int(F);
+    FusedArgs a = fused_args(g, t, x, y, int(S), T, ld_x, ld_y, F, out_len);
     a.cs = channels;
-    choose_chunks_rounds(F, a.n_streams, g.n / g.h + 1, fused_resident_waves() * pair_waves_per_cu() / 16,
-                         a.n_chunks, a.M);
-    chunk_override(F, a);
-    note_chunks(a.n_chunks);
-    a.ring_blocks = g.ring_len / g.h;
-    a.pad = g.pad;
-    a.pad_mode = g.pad_mode;
-    a.inv_n = g.inv_n;
-    a.gain = g.gain;
+    choose_chunks_rounds(F, a.n_streams, g.n / g.h + 1, device_cus() * pair_waves_per_cu(), a.n_chunks, a.M);
     return launch_pair(g.h / 64, a, S * a.n_chunks, stream);
 }
 
@@ -2184,11 +1951,7 @@ template <int SH>
 static hipError_t pair4k_sh(const FusedArgs& a, int64_t grid, hipStream_t stream) {
     constexpr int NB = 16 / SH;
     auto k = a.t.gain ? k_stft_ola_pair4k<SH, NB, true> : k_stft_ola_pair4k<SH, NB, false>;
-    hipError_t e = set_lds(k, kPair4kLds);
-    if (e != hipSuccess) return e;
-    note_launch(CRLOT_K_PAIR4K, grid);
-    hipLaunchKernelGGL(k, dim3(unsigned(grid)), dim3(256), kPair4kLds, stream, a);
-    return hipGetLastError();
+    return launch_kernel(k, CRLOT_K_PAIR4K, grid, 256, kPair4kLds, stream, a);
 }
 
 // Workgroup walker: N = 16 L (E = 8), H = 2 L S.
@@ -2196,12 +1959,7 @@ template <int L, int S>
 static hipError_t fused_wg_ls(const FusedArgs& a, int64_t grid, hipStream_t stream) {
     constexpr int NB = 8 / S;
     auto k = a.t.gain ? k_stft_ola_wg<L, S, NB, true> : k_stft_ola_wg<L, S, NB, false>;
-    const size_t lds = sizeof(cf) * 3 * 8 * L;
-    hipError_t e = set_lds(k, lds);
-    if (e != hipSuccess) return e;
-    note_launch(CRLOT_K_FUSED_WG, grid);
-    hipLaunchKernelGGL(k, dim3(unsigned(grid)), dim3(L), lds, stream, a);
-    return hipGetLastError();
+    return launch_kernel(k, CRLOT_K_FUSED_WG, grid, L, sizeof(cf) * 3 * 8 * L, stream, a);
 }
 
 template <int L>
@@ -2233,36 +1991,13 @@ hipError_t launch_fused_wg(const Geometry& g, const DevTables& t, const float* x
                            int n_streams, int64_t T, int64_t ld_x, int64_t ld_y, int64_t F,
                            int64_t out_len, hipStream_t stream) {
     if (!fused_wg_supported(g.n, g.h) || F <= 0 || n_streams <= 0) return hipErrorInvalidValue;
-    FusedArgs a;
-    a.t = t;
-    a.x = x;
-    a.y = y;
-    a.ld_x = ld_x;
-    a.ld_y = ld_y;
-    a.T = int(T);
-    a.out_len = int(out_len);
-    a.n_streams = n_streams;
-    a.F = int(F);
-    const int target = wg_chunk_target();
-    a.n_chunks = int((F + target - 1) / target);
-    a.M = int((F + a.n_chunks - 1) / a.n_chunks);
-    a.n_chunks = int((F + a.M - 1) / a.M);
-    chunk_override(F, a);
-    note_chunks(a.n_chunks);
-    a.ring_blocks = g.ring_len / g.h;
-    a.pad = g.pad;
-    a.pad_mode = g.pad_mode;
-    a.inv_n = g.inv_n;
-    a.gain = g.gain;
+    FusedArgs a = fused_args(g, t, x, y, n_streams, T, ld_x, ld_y, F, out_len);
     if (g.n == 4096 && t.ptw4 && t.pden4 && t.wsn && t.rden && (g.h == 512 || g.h == 1024 || g.h == 2048)) {
         // K_pair4k: whole resident rounds of workgroups (three per CU with the
         // three-workgroup hot walker, else two)
         const bool hot = (!t.gain || g.h == 1024) && a.pad_mode == 0 && !pair4k_hot_disabled() && a.t.hot;
         const bool hot3 = hot && !t.gain && g.h == 1024 && pair4k_hot3();
-        choose_chunks_rounds(F, n_streams, g.n / g.h + 1, fused_resident_waves() / 16 * (hot3 ? 3 : 2), a.n_chunks,
-                             a.M);
-        chunk_override(F, a);
-        note_chunks(a.n_chunks);
+        choose_chunks_rounds(F, n_streams, g.n / g.h + 1, device_cus() * (hot3 ? 3 : 2), a.n_chunks, a.M);
         const int64_t grid4 = int64_t(n_streams) * a.n_chunks;
         if (!t.pflags || t.pflags_len < grid4) return hipErrorInvalidValue;
         // the paired-only hot walker, then the two-regime walker over the chunks it
@@ -2282,6 +2017,7 @@ hipError_t launch_fused_wg(const Geometry& g, const DevTables& t, const float* x
             default: return hipErrorInvalidValue;
         }
     }
+    choose_chunks_fixed(F, wg_chunk_target(), a.n_chunks, a.M);
     const int64_t grid = int64_t(n_streams) * a.n_chunks;
     const int L = g.n / 16, s = g.h / (2 * L);
     switch (L) {
@@ -2391,12 +2127,8 @@ static hipError_t launch_any(K kernel, AnyArgs& a, int64_t items, hipStream_t st
                              int32_t id = CRLOT_K_FFT_ANY) {
     a.waves_per_block = any_waves_per_block(a.pl.p);
     const size_t lds = any_lds_bytes(a.pl.p, a.tw_len, a.waves_per_block, tables);
-    hipError_t e = set_lds(kernel, lds);
-    if (e != hipSuccess) return e;
     const int64_t grid = (items + a.waves_per_block - 1) / a.waves_per_block;
-    note_launch(id, grid);
-    hipLaunchKernelGGL(kernel, dim3(unsigned(grid)), dim3(64 * a.waves_per_block), lds, stream, a);
-    return hipGetLastError();
+    return launch_kernel(kernel, id, grid, 64 * a.waves_per_block, lds, stream, a);
 }
 
 hipError_t launch_synth_any(const Geometry& g, const DevTables& t, const float* twany,
@@ -2469,23 +2201,13 @@ hipError_t launch_fused_any(const Geometry& g, const DevTables& t, const float* 
     }
     if (w < 1) return hipErrorInvalidValue;  // too large for one CU: staged path
     a.waves_per_block = w;
-    const int nb = (g.n + g.h - 1) / g.h;
-    const int resident = fused_resident_waves() / 16 * per_cu * w;  // CUs x walkers per CU
-    choose_chunks(F, n_streams, nb, resident, f.n_chunks, f.M);
-    if (const int64_t c = chunks_or(0, F); c > 0) {  // the plan's chunk knob
-        f.M = int((F + c - 1) / c);
-        f.n_chunks = int((F + f.M - 1) / f.M);
-    }
-    if (!mask) note_chunks(f.n_chunks);  // (a redo walk keeps the pair walker's record)
+    const int resident = device_cus() * per_cu * w;  // CUs x walkers per CU
+    choose_chunks(F, n_streams, resident, f.n_chunks, f.M, /*record=*/!mask);  // (a redo walk keeps the pair walker's)
     const size_t lds = tables + size_t(w) * per_wave;
     const int64_t waves = int64_t(n_streams) * f.n_chunks;
     const int64_t grid = (waves + w - 1) / w;
     auto k = t.gain ? k_stft_ola_any<true> : k_stft_ola_any<false>;
-    hipError_t e = set_lds(k, lds);
-    if (e != hipSuccess) return e;
-    note_launch(CRLOT_K_FUSED_ANY, grid);
-    hipLaunchKernelGGL(k, dim3(unsigned(grid)), dim3(64 * w), lds, stream, f);
-    return hipGetLastError();
+    return launch_kernel(k, CRLOT_K_FUSED_ANY, grid, 64 * w, lds, stream, f);
 }
 
 hipError_t launch_stream_any(const Geometry& g, const DevTables& t, const float* twany,
@@ -2498,10 +2220,7 @@ hipError_t launch_stream_any(const Geometry& g, const DevTables& t, const float*
         return hipErrorInvalidValue;
     const int w = f.a.waves_per_block;
     auto kern = t.gain ? k_stream_any<true> : k_stream_any<false>;
-    hipError_t e = set_lds(kern, lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(unsigned((channels + w - 1) / w)), dim3(64 * w), lds, stream, f);
-    return hipGetLastError();
+    return launch_kernel(kern, kNoRecord, (channels + w - 1) / w, 64 * w, lds, stream, f);
 }
 
 bool fk::stream_any_args(const Geometry& g, const DevTables& t, const float* twany, const float* in, int64_t in_ld,
@@ -2583,20 +2302,9 @@ hipError_t launch_fft_any(int kind, int p, float inv_scale, const DevTables& t, 
 template <int E>
 static hipError_t synth_e(const SynthArgs& a, int64_t grid, hipStream_t stream) {
     const size_t lds = Lds<E>::bytes;
-    if (a.spec) {
-        auto k = a.t.gain ? k_synth_frames<E, true, true> : k_synth_frames<E, false, true>;
-        hipError_t e = set_lds(k, lds);
-        if (e != hipSuccess) return e;
-        note_launch(CRLOT_K_SYNTH, grid);
-        hipLaunchKernelGGL(k, dim3(unsigned(grid)), dim3(kBlock), lds, stream, a);
-    } else {
-        auto k = a.t.gain ? k_synth_frames<E, true, false> : k_synth_frames<E, false, false>;
-        hipError_t e = set_lds(k, lds);
-        if (e != hipSuccess) return e;
-        note_launch(CRLOT_K_SYNTH, grid);
-        hipLaunchKernelGGL(k, dim3(unsigned(grid)), dim3(kBlock), lds, stream, a);
-    }
-    return hipGetLastError();
+    auto k = a.spec ? (a.t.gain ? k_synth_frames<E, true, true> : k_synth_frames<E, false, true>)
+                    : (a.t.gain ? k_synth_frames<E, true, false> : k_synth_frames<E, false, false>);
+    return launch_kernel(k, CRLOT_K_SYNTH, grid, kBlock, lds, stream, a);
 }
 
 hipError_t launch_synth_frames(const Geometry& g, const DevTables& t, const float* x,
@@ -2660,25 +2368,20 @@ hipError_t launch_ola_gather(const Geometry& g, const DevTables& t, const float*
             return e ? std::atoi(e) : 0;
         }();
         const int bpb = bpb_env > 0 ? bpb_env : std::max(1, 1024 / g.h);  // >= 1024 outputs per workgroup
-        note_launch(CRLOT_K_GATHER, (F + bpb - 1) / bpb * n_streams);
-        hipLaunchKernelGGL(kg, dim3(unsigned((F + bpb - 1) / bpb), unsigned(n_streams)), dim3(threads), 0, stream,
-                           a, bpb);
-        return hipGetLastError();
+        return launch_kernel_plain(kg, CRLOT_K_GATHER, dim3(unsigned((F + bpb - 1) / bpb), unsigned(n_streams)),
+                                   dim3(threads), 0, stream, a, bpb);
     }
     if (n_streams <= 65535 && out_len < (int64_t(1) << 31) - 256 && int64_t(g.h) + 256 < (1 << 24)) {
         // one sample per thread (two per thread measured 5-15 % slower: occupancy)
         auto kg = (g.n + g.h - 1) / g.h <= 4 ? k_ola_gather2<1, 4> : k_ola_gather2<1, 8>;
         const int64_t per_block = 256;
-        note_launch(CRLOT_K_GATHER, (out_len + per_block - 1) / per_block * n_streams);
-        hipLaunchKernelGGL(kg, dim3(unsigned((out_len + per_block - 1) / per_block), unsigned(n_streams)),
-                           dim3(256), 0, stream, a);
-        return hipGetLastError();
+        return launch_kernel_plain(kg, CRLOT_K_GATHER,
+                                   dim3(unsigned((out_len + per_block - 1) / per_block), unsigned(n_streams)),
+                                   dim3(256), 0, stream, a);
     }
     const int64_t total = int64_t(n_streams) * out_len;
     const int64_t grid = (total + 255) / 256;
-    note_launch(CRLOT_K_GATHER, grid);
-    hipLaunchKernelGGL(k_ola_gather, dim3(unsigned(grid)), dim3(256), 0, stream, a);
-    return hipGetLastError();
+    return launch_kernel_plain(k_ola_gather, CRLOT_K_GATHER, dim3(unsigned(grid)), dim3(256), 0, stream, a);
 }
 
 hipError_t launch_ola_gather_wrap(const Geometry& g, const DevTables& t, const float* frames, int64_t ld_frames,
@@ -2698,9 +2401,8 @@ hipError_t launch_ola_gather_wrap(const Geometry& g, const DevTables& t, const f
     a.gain = g.gain;
     const int64_t y_len = y_blocks ? len : 0;
     const int64_t grid = (y_len + int64_t(g.ring_len) + 255) / 256;
-    note_launch(CRLOT_K_GATHER, grid);
-    hipLaunchKernelGGL(k_ola_gather_wrap, dim3(unsigned(grid)), dim3(256), 0, stream, a, acc, y, len, y_len);
-    return hipGetLastError();
+    return launch_kernel_plain(k_ola_gather_wrap, CRLOT_K_GATHER, dim3(unsigned(grid)), dim3(256), 0, stream, a, acc, y,
+                               len, y_len);
 }
 
 template <int E>
@@ -2708,11 +2410,7 @@ static hipError_t rfft_irfft_e(const FftArgs& a, float* r, float* r_host, int64_
     constexpr int P = 64 * E;
     const size_t lds = lds_bytes_fft<E>() + sizeof(cf) * kWaves * (P + 1);
     const int64_t grid = (int64_t(a.batch) + kWaves - 1) / kWaves;
-    hipError_t e = set_lds(k_rfft_irfft<E>, lds);
-    if (e != hipSuccess) return e;
-    note_launch(CRLOT_K_FFT, grid);
-    hipLaunchKernelGGL(k_rfft_irfft<E>, dim3(unsigned(grid)), dim3(kBlock), lds, stream, a, r, r_host, ld_r);
-    return hipGetLastError();
+    return launch_kernel(k_rfft_irfft<E>, CRLOT_K_FFT, grid, kBlock, lds, stream, a, r, r_host, ld_r);
 }
 
 hipError_t launch_rfft_irfft(const Geometry& g, const DevTables& t, const float* in, int64_t ld_in, float* spec,
@@ -2742,11 +2440,7 @@ static hipError_t fft_e(const FftArgs& a, hipStream_t stream) {
     const size_t lds = lds_bytes_fft<E>();
     const int64_t grid = (int64_t(a.batch) + kWaves - 1) / kWaves;
     auto k = CPLX ? k_cfft<E, INV> : INV ? k_irfft<E> : k_rfft<E>;
-    hipError_t e = set_lds(k, lds);
-    if (e != hipSuccess) return e;
-    note_launch(CRLOT_K_FFT, grid);
-    hipLaunchKernelGGL(k, dim3(unsigned(grid)), dim3(kBlock), lds, stream, a);
-    return hipGetLastError();
+    return launch_kernel(k, CRLOT_K_FFT, grid, kBlock, lds, stream, a);
 }
 
 template <bool INV, bool CPLX = false>
@@ -2777,12 +2471,7 @@ static hipError_t fft_dispatch(const Geometry& g, const DevTables& t, const floa
 template <int E, int S>
 static hipError_t stream_es(const StreamArgs& a, hipStream_t stream) {
     auto k = a.t.gain ? k_stream_hop<E, S, true> : k_stream_hop<E, S, false>;
-    const size_t lds = Lds<E>::bytes;
-    hipError_t e = set_lds(k, lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k, dim3(unsigned((a.channels + kWaves - 1) / kWaves)), dim3(kBlock), lds,
-                       stream, a);
-    return hipGetLastError();
+    return launch_kernel(k, kNoRecord, (a.channels + kWaves - 1) / kWaves, kBlock, Lds<E>::bytes, stream, a);
 }
 
 template <int E>

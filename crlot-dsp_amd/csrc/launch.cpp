@@ -1,10 +1,13 @@
 // launch.cpp -- per-call launch knobs and launch records (kernels.h LaunchCtl),
-// and the names of the CRLOT_K_* kernel ids (include/crlot_dsp.h).
+// the compute-unit count and the chunk policies of the launch layer
+// (launch_common.h), and the names of the CRLOT_K_* kernel ids (include/crlot_dsp.h).
 #include <algorithm>
+#include <atomic>
 #include <cstdint>
 
 #include "crlot_dsp.h"
 #include "kernels.h"
+#include "launch_common.h"
 
 namespace crlot {
 namespace {
@@ -33,6 +36,105 @@ int64_t chunks_or(int64_t dflt, int64_t max_chunks) {
     const LaunchCtl* c = tl_ctl;
     if (!c || c->chunks <= 0) return dflt;
     return std::max<int64_t>(1, std::min<int64_t>(c->chunks, max_chunks));
+}
+
+int device_cus() {
+    constexpr int kMaxDev = 64;
+    static std::atomic<int> cache[kMaxDev];  // per device id; 0: not asked yet
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 256;
+    const bool cached = dev >= 0 && dev < kMaxDev;
+    if (cached && (n = cache[dev].load(std::memory_order_relaxed)) > 0) return n;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+    if (cached) cache[dev].store(n, std::memory_order_relaxed);
+    return n;
+}
+
+// ------------------------------------------------------------------ chunk policies
+namespace {
+// n chunks asked for -> chunks of m = ceil(F / n) frames, n_chunks of them
+void split(int64_t F, int64_t n, bool even, int& n_chunks, int& m) {
+    int64_t len = (F + n - 1) / n;
+    if (even) len += len & 1;
+    m = int(len);
+    n_chunks = int((F + len - 1) / len);
+}
+// The plan's chunk knob (crlot_plan_set_chunks, via the call's LaunchCtl)
+// replaces a policy's chunking: min(knob, F) chunks per stream.
+void apply_knob(int64_t F, int& n_chunks, int& m) {
+    if (const int64_t n = chunks_or(0, F); n > 0) split(F, n, false, n_chunks, m);
+}
+}  // namespace
+
+// Split each stream's F frames into n chunks (one wave each; NB-1 halo frames
+// recomputed per chunk).  Measured on MI355X (scripts/sweep_chunks.sh): ~128-frame
+// chunks are right while the grid is several resident rounds deep (headline:
+// flat for 12..24 chunks), but a small batch must still fill the device -- at
+// least one resident round of waves, two when chunks stay >= 48 frames (config 2:
+// +5 %, config 4 batched: +20 % over fixed 128-frame chunks).
+void choose_chunks(int64_t F, int n_streams, int resident, int& n_chunks, int& m, bool record) {
+    const int64_t S = std::max(1, n_streams);
+    int64_t n = (F + 127) / 128;
+    n = std::max<int64_t>(n, (resident + S - 1) / S);
+    const int64_t two = (2 * resident + S - 1) / S;
+    if (two > n && F / two >= 48) n = two;
+    n = std::max<int64_t>(1, std::min<int64_t>(n, std::max<int64_t>(1, F / 32)));
+    split(F, n, false, n_chunks, m);
+    apply_knob(F, n_chunks, m);
+    if (record) note_chunks(n_chunks);
+}
+
+// K_pair*: whole resident rounds.  A pair kernel's workgroup only frees its
+// slots when all of its waves finish, so a grid that ends in a partial round
+// idles the device for a whole chunk's time (headline, 16 waves/CU: 15 chunks
+// = 3.75 rounds 219k Msamples/s, 8 chunks = 2 rounds 232k).  Among chunk counts
+// with chunks of >= 48 frames, the fewest (rounds + 0.1) x (frames + halo + 10)
+// per wave: the 0.1 charges a single long round for its tail, the 10 a wave's
+// start-up (tables, first hops) (measured: headline 6 chunks = 2 rounds best,
+// 9-15 within 1-3 %; config-4 shape 64 chunks = one round best).
+void choose_chunks_rounds(int64_t F, int n_streams, int halo, int resident, int& n_chunks, int& m,
+                          bool small_batches) {
+    const int64_t S = std::max(1, n_streams), R = std::max(1, resident);
+    const int64_t hi = std::max<int64_t>(1, F / 48);
+    const int64_t lo = std::min(hi, (F + 511) / 512);
+    int64_t best_n = lo;
+    double best_cost = 1e300;
+    for (int64_t n = lo; n <= hi; ++n) {
+        const int64_t mm = (F + n - 1) / n, nc = (F + mm - 1) / mm;
+        const double cost = (double((S * nc + R - 1) / R) + 0.1) * double(mm + halo + 10);
+        if (cost < best_cost) best_cost = cost, best_n = n;
+    }
+    split(F, best_n, false, n_chunks, m);
+    // a batch below one resident round (one window of a few streams: the per-call
+    // latency case) walks chunks of >= 8 frames instead, as many as fit the round
+    if (small_batches && S * n_chunks < resident) {
+        const int64_t n = std::min<int64_t>(F / 8, (resident + S - 1) / S);
+        if (n > n_chunks) split(F, n, false, n_chunks, m);
+    }
+    apply_knob(F, n_chunks, m);
+    note_chunks(n_chunks);
+}
+
+void choose_chunks_fixed(int64_t F, int target, int& n_chunks, int& m) {
+    split(F, (F + target - 1) / target, false, n_chunks, m);
+    apply_knob(F, n_chunks, m);
+    note_chunks(n_chunks);
+}
+
+// Walkers without a halo worth amortising (the forward walks) or whose grids are
+// small (the odd sizes): about two resident rounds of them, chunks no shorter than
+// F / cap frames.  kChunkFill128 keeps chunks of about 128 frames while the grid
+// stays that deep (K_stft, K_istft, K_pair_stft, the feature walkers); the
+// K_pair15 / K_pairN / K_pair30 walkers and their spectral forms do not.
+void choose_chunks_two_rounds(int64_t F, int64_t units, int64_t resident, int64_t cap, unsigned flags, int& n_chunks,
+                              int& m, int64_t knob_max) {
+    const int64_t U = std::max<int64_t>(1, units);
+    int64_t n = (2 * std::max<int64_t>(1, resident) + U - 1) / U;
+    if (flags & kChunkFill128) n = std::max<int64_t>(n, (F + 127) / 128);
+    n = std::max<int64_t>(1, std::min<int64_t>(n, cap));
+    n = chunks_or(n, knob_max > 0 ? knob_max : F);
+    split(F, n, (flags & kChunkEven) != 0, n_chunks, m);
+    note_chunks(n_chunks);
 }
 
 }  // namespace crlot

@@ -26,6 +26,7 @@
 #include <cstdint>
 
 #include "kernels.h"
+#include "launch_common.h"
 
 namespace crlot {
 namespace {
@@ -254,17 +255,16 @@ hipError_t launch_bin_gain(const float* spec, float* out, const float* g, int64_
                            hipStream_t s) {
     if (rows <= 0 || bins <= 0) return hipSuccess;
     if (rows * bins > (int64_t(1) << 40) || (ld & 1)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_bin_gain, dim3(unsigned((rows * bins + 255) / 256)), dim3(256), 0, s, spec, out, g, rows, ld,
-                       bins);
-    return hipGetLastError();
+    return fk::launch_kernel_plain(k_bin_gain, fk::kNoRecord, dim3(unsigned((rows * bins + 255) / 256)), dim3(256), 0,
+                                   s, spec, out, g, rows, ld, bins);
 }
 
 hipError_t launch_windowed_frames(const float* x, int64_t T, const float* w, float* p, int64_t F, int64_t N,
                                   int64_t H, hipStream_t s) {
     if (F <= 0 || N <= 0) return hipSuccess;
     if (F * N > (int64_t(1) << 40)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_windowed_frames, dim3(unsigned((F * N + 255) / 256)), dim3(256), 0, s, x, T, w, p, F, N, H);
-    return hipGetLastError();
+    return fk::launch_kernel_plain(k_windowed_frames, fk::kNoRecord, dim3(unsigned((F * N + 255) / 256)), dim3(256), 0,
+                                   s, x, T, w, p, F, N, H);
 }
 
 hipError_t launch_axpy(float* dst, int64_t ld_dst, const float* src, int64_t ld_src, const float* win, float g,
@@ -278,8 +278,7 @@ hipError_t launch_axpy(float* dst, int64_t ld_dst, const float* src, int64_t ld_
     const dim3 grid(unsigned((n + per - 1) / per), unsigned(batch));
     auto k = vec ? (win ? k_axpy<true, true> : k_axpy<true, false>)
                  : (win ? k_axpy<false, true> : k_axpy<false, false>);
-    hipLaunchKernelGGL(k, grid, dim3(256), 0, s, dst, ld_dst, src, ld_src, win, g, n);
-    return hipGetLastError();
+    return fk::launch_kernel_plain(k, fk::kNoRecord, grid, dim3(256), 0, s, dst, ld_dst, src, ld_src, win, g, n);
 }
 
 hipError_t launch_normalize_and_clear(float* out, int64_t ld_out, float* acc, int64_t ld_acc, const float* norm,
@@ -292,8 +291,7 @@ hipError_t launch_normalize_and_clear(float* out, int64_t ld_out, float* acc, in
     const int64_t per = vec ? 1024 : 256;
     const dim3 grid(unsigned((n + per - 1) / per), unsigned(batch));
     auto k = vec ? k_normalize_and_clear<true> : k_normalize_and_clear<false>;
-    hipLaunchKernelGGL(k, grid, dim3(256), 0, s, out, ld_out, acc, ld_acc, norm, eps, n);
-    return hipGetLastError();
+    return fk::launch_kernel_plain(k, fk::kNoRecord, grid, dim3(256), 0, s, out, ld_out, acc, ld_acc, norm, eps, n);
 }
 
 hipError_t launch_fq_frames(const float* x, int64_t T, int64_t ld_x, int n_streams, float* frames, int64_t F,
@@ -301,8 +299,8 @@ hipError_t launch_fq_frames(const float* x, int64_t T, int64_t ld_x, int n_strea
     if (F <= 0 || n_streams <= 0) return hipSuccess;
     if (n_streams > 65535 || F * N > (int64_t(1) << 40)) return hipErrorInvalidValue;
     const dim3 grid(unsigned((F * N + 255) / 256), unsigned(n_streams));
-    hipLaunchKernelGGL(k_fq_frames, grid, dim3(256), 0, s, x, T, ld_x, frames, F, N, H, pad, pad_mode);
-    return hipGetLastError();
+    return fk::launch_kernel_plain(k_fq_frames, fk::kNoRecord, grid, dim3(256), 0, s, x, T, ld_x, frames, F, N, H, pad,
+                                   pad_mode);
 }
 
 hipError_t launch_deinterleave(const float* x, int64_t ld_x, float* planes, int groups, int64_t T, int C,
@@ -310,10 +308,9 @@ hipError_t launch_deinterleave(const float* x, int64_t ld_x, float* planes, int 
     if (groups <= 0 || T <= 0) return hipSuccess;
     const int tr = ilv_rows(C);
     const size_t lds = sizeof(float) * size_t(tr) * (C + 1);
-    note_launch(CRLOT_K_DEINTERLEAVE, (T + tr - 1) / tr * groups);
-    hipLaunchKernelGGL(k_deinterleave, dim3(unsigned((T + tr - 1) / tr), unsigned(groups)), dim3(256), lds, s,
-                       x, ld_x, planes, T, C);
-    return hipGetLastError();
+    return fk::launch_kernel_plain(k_deinterleave, CRLOT_K_DEINTERLEAVE,
+                                   dim3(unsigned((T + tr - 1) / tr), unsigned(groups)), dim3(256), lds, s, x, ld_x,
+                                   planes, T, C);
 }
 
 hipError_t launch_interleave(const float* planes, int64_t L, float* y, int64_t ld_y, int groups, int C,
@@ -321,10 +318,9 @@ hipError_t launch_interleave(const float* planes, int64_t L, float* y, int64_t l
     if (groups <= 0 || L <= 0) return hipSuccess;
     const int tr = ilv_rows(C);
     const size_t lds = sizeof(float) * size_t(tr) * (C + 1);
-    note_launch(CRLOT_K_INTERLEAVE, (L + tr - 1) / tr * groups);
-    hipLaunchKernelGGL(k_interleave, dim3(unsigned((L + tr - 1) / tr), unsigned(groups)), dim3(256), lds, s,
-                       planes, L, y, ld_y, C);
-    return hipGetLastError();
+    return fk::launch_kernel_plain(k_interleave, CRLOT_K_INTERLEAVE,
+                                   dim3(unsigned((L + tr - 1) / tr), unsigned(groups)), dim3(256), lds, s, planes, L, y,
+                                   ld_y, C);
 }
 
 hipError_t launch_ola_add(float* ring, int channels, int64_t R, const float* src, int64_t cs,
@@ -332,8 +328,8 @@ hipError_t launch_ola_add(float* ring, int channels, int64_t R, const float* src
                           hipStream_t s) {
     if (len <= 0 || channels <= 0) return hipSuccess;
     const dim3 grid(unsigned((len + 255) / 256), unsigned(channels));
-    hipLaunchKernelGGL(k_ola_add, grid, dim3(256), 0, s, ring, R, src, cs, js, win, start, len, gain);
-    return hipGetLastError();
+    return fk::launch_kernel_plain(k_ola_add, fk::kNoRecord, grid, dim3(256), 0, s, ring, R, src, cs, js, win, start,
+                                   len, gain);
 }
 
 hipError_t launch_ola_produce(float* ring, int channels, int64_t R, const float* den, float* out,
@@ -342,9 +338,8 @@ hipError_t launch_ola_produce(float* ring, int channels, int64_t R, const float*
     const int64_t span = peak && n_total > len ? n_total : len;
     if (span <= 0 || channels <= 0) return hipSuccess;
     const dim3 grid(unsigned((span + 255) / 256), unsigned(channels));
-    hipLaunchKernelGGL(k_ola_produce, grid, dim3(256), 0, s, ring, R, den, out, ldo, rp, len, n_total,
-                       peak);
-    return hipGetLastError();
+    return fk::launch_kernel_plain(k_ola_produce, fk::kNoRecord, grid, dim3(256), 0, s, ring, R, den, out, ldo, rp, len,
+                                   n_total, peak);
 }
 
 }  // namespace crlot

@@ -38,7 +38,7 @@
 #include <type_traits>
 
 #include "fft_pair15.h"
-#include "fused_common.h"
+#include "launch_common.h"
 
 namespace crlot {
 namespace fk {
@@ -637,32 +637,15 @@ __global__ __launch_bounds__(64 * kQW, 2) void k_p15_mask(const PairSpecArgs pa)
 template <typename K>
 hipError_t q15_launch(K kernel, const PairSpecArgs& a, int n, int64_t waves, int32_t kind, bool ring,
                       hipStream_t stream) {
-    const size_t lds = Q15Lds::bytes(n, a.f.hop, ring);
-    hipError_t e = set_lds(kernel, lds);
-    if (e != hipSuccess) return e;
-    const int64_t grid = (waves + kQW - 1) / kQW;
-    note_launch(kind, grid);
-    hipLaunchKernelGGL(kernel, dim3(unsigned(grid)), dim3(64 * kQW), lds, stream, a);
-    return hipGetLastError();
+    return launch_kernel(kernel, kind, (waves + kQW - 1) / kQW, 64 * kQW, Q15Lds::bytes(n, a.f.hop, ring), stream, a);
 }
 
 // chunks: about two resident rounds of walks, each >= `min_m` frames, an even
 // length; returns the waves to launch (stream units x chunks)
 int64_t q15_chunks(FusedArgs& f, int n, int64_t F, int n_streams, int64_t min_m) {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-        cus = 256;
     const int halves = n == 480 ? 2 : 1;
     const int64_t units = std::max(1, (n_streams + halves - 1) / halves);
-    const int64_t resident = int64_t(cus) * 2 * kQW;
-    int64_t c = std::max<int64_t>(1, std::min<int64_t>(F / min_m, (2 * resident + units - 1) / units));
-    c = chunks_or(c, F);
-    int64_t m = (F + c - 1) / c;
-    m += m & 1;
-    f.M = int(m);
-    f.n_chunks = int((F + m - 1) / m);
-    note_chunks(f.n_chunks);
+    choose_chunks_two_rounds(F, units, int64_t(device_cus()) * 2 * kQW, F / min_m, kChunkEven, f.n_chunks, f.M);
     return units * f.n_chunks;
 }
 
@@ -687,19 +670,7 @@ hipError_t launch_pair15_stft(const Geometry& g, const DevTables& t, const float
     if (!pair15_spec_supported(g.n, g.h, g.ring_len) || F <= 0 || n_streams <= 0 || !t.ptw || !t.wa ||
         !pair15_spec_fits(g.n, ld_x, T))
         return hipErrorInvalidValue;
-    fk::PairSpecArgs a{};
-    a.f.t = t;
-    a.f.x = x;
-    a.f.ld_x = ld_x;
-    a.f.T = int(T);
-    a.f.n_streams = n_streams;
-    a.f.F = int(F);
-    a.f.hop = g.h;
-    a.f.pad = g.pad;
-    a.f.pad_mode = g.pad_mode;
-    a.spec = spec;
-    a.ld_spec = ld_spec;
-    a.ld_frame = ld_frame;
+    fk::PairSpecArgs a = fk::pair_stft_args(g, t, x, n_streams, T, ld_x, F, spec, ld_spec, ld_frame);
     const int64_t waves = fk::q15_chunks(a.f, g.n, F, n_streams, 32);
     return g.n == 960 ? fk::q15_launch(fk::k_p15_stft<64>, a, g.n, waves, CRLOT_K_PAIR_STFT, false, stream)
                       : fk::q15_launch(fk::k_p15_stft<32>, a, g.n, waves, CRLOT_K_PAIR_STFT, false, stream);
@@ -712,21 +683,7 @@ hipError_t launch_pair15_istft(const Geometry& g, const DevTables& t, const Spec
     if (!pair15_spec_supported(g.n, g.h, g.ring_len) || F <= 0 || n_streams <= 0 || !t.ptw || !t.ws || !t.den ||
         !pair15_spec_fits(g.n, ld_y, F * g.h + g.n))
         return hipErrorInvalidValue;
-    fk::PairSpecArgs a{};
-    a.f.t = t;
-    a.f.y = y;
-    a.f.ld_y = ld_y;
-    a.f.out_len = int(F * g.h);
-    a.f.n_streams = n_streams;
-    a.f.F = int(F);
-    a.f.hop = g.h;
-    a.f.ring_blocks = g.ring_len / g.h;
-    a.f.inv_n = g.inv_n;
-    a.f.gain = g.gain;
-    a.sin = spec;
-    a.ld_spec = ld_spec;
-    a.ld_frame = ld_frame;
-    a.mask = m;
+    fk::PairSpecArgs a = fk::pair_istft_args(g, t, m, spec, ld_spec, ld_frame, y, n_streams, F, ld_y);
     const int64_t waves = fk::q15_chunks(a.f, g.n, F, n_streams, 48);
     const int32_t K = CRLOT_K_PAIR_ISTFT;
     if (g.n == 480)
@@ -746,23 +703,7 @@ hipError_t launch_pair15_masked(const Geometry& g, const DevTables& t, const Spe
     if (!pair15_spec_supported(g.n, g.h, g.ring_len) || F <= 0 || n_streams <= 0 || !m.p || !t.ptw || !t.wa ||
         !t.ws || !t.den || !pair15_spec_fits(g.n, ld_x, T) || !pair15_spec_fits(g.n, ld_y, out_len + g.n))
         return hipErrorInvalidValue;
-    fk::PairSpecArgs a{};
-    a.f.t = t;
-    a.f.x = x;
-    a.f.y = y;
-    a.f.ld_x = ld_x;
-    a.f.ld_y = ld_y;
-    a.f.T = int(T);
-    a.f.out_len = int(out_len);
-    a.f.n_streams = n_streams;
-    a.f.F = int(F);
-    a.f.hop = g.h;
-    a.f.ring_blocks = g.ring_len / g.h;
-    a.f.pad = g.pad;
-    a.f.pad_mode = g.pad_mode;
-    a.f.inv_n = g.inv_n;
-    a.f.gain = g.gain;
-    a.mask = m;
+    fk::PairSpecArgs a = fk::pair_masked_args(g, t, m, x, y, n_streams, T, ld_x, ld_y, F, out_len);
     const int64_t waves = fk::q15_chunks(a.f, g.n, F, n_streams, 48);
     return g.n == 960 ? fk::q15_launch(fk::k_p15_mask<64>, a, g.n, waves, CRLOT_K_PAIR_MASK, true, stream)
                       : fk::q15_launch(fk::k_p15_mask<32>, a, g.n, waves, CRLOT_K_PAIR_MASK, true, stream);

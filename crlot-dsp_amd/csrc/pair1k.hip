@@ -7,7 +7,7 @@
 #include <utility>
 
 #include "fft_pair.h"
-#include "fused_common.h"
+#include "launch_common.h"
 #include "ola_pair.h"
 
 namespace crlot {
@@ -781,6 +781,7 @@ hipError_t pair_sh(const FusedArgs& a, int64_t waves, hipStream_t stream) {
     constexpr int NB = 16 / SH, W = kPairWaves;
     const size_t lds = PairLds<W>::bytes;
     const int64_t grid = (waves + W - 1) / W;
+    const dim3 grid3 = dim3(unsigned(grid)), block3 = dim3(64 * W);  // (kf's launches: its LDS limit is raised once)
     hipError_t e;
     if (ILV && (a.cs < 1 || a.pad_mode != 0)) return hipErrorInvalidValue;
     auto kf = a.t.gain ? k_stft_ola_pair_fix<SH, NB, W, true, ILV> : k_stft_ola_pair_fix<SH, NB, W, false, ILV>;
@@ -790,30 +791,21 @@ hipError_t pair_sh(const FusedArgs& a, int64_t waves, hipStream_t stream) {
 #ifdef CRLOT_PAIR32_EXPERIMENT
         if (!ILV && pair32_enabled() && a.pad_mode == 0 && a.t.hot && !a.t.gain) {
             if ((e = launch_pair32(a, stream)) != hipSuccess) return e;
-            note_launch(CRLOT_K_PAIR_FIX, grid);
-            hipLaunchKernelGGL(kf, dim3(unsigned(grid)), dim3(64 * W), lds, stream, a);
-            return hipGetLastError();
+            return launch_kernel_plain(kf, CRLOT_K_PAIR_FIX, grid3, block3, lds, stream, a);
         }
 #endif
         if (a.pad_mode == 0 && a.t.hot && (!a.t.gain || CRLOT_PAIR_REG_TW)) {
             if (CRLOT_PAIR_PKA && !a.t.pden2) return hipErrorInvalidValue;
             if (a.t.pflags_len < 2 * waves) return hipErrorInvalidValue;  // two flag words per walker
             auto k = a.t.gain ? k_stft_ola_pair<SH, NB, W, ILV, CRLOT_PAIR_REG_TW != 0> : k_stft_ola_pair<SH, NB, W, ILV, false>;
-            if ((e = set_lds(k, lds)) != hipSuccess) return e;
-            note_launch(CRLOT_K_PAIR_HOT, grid);
-            hipLaunchKernelGGL(k, dim3(unsigned(grid)), dim3(64 * W), lds, stream, a);
-            if ((e = hipGetLastError()) != hipSuccess) return e;
+            if ((e = launch_kernel(k, CRLOT_K_PAIR_HOT, grid, 64 * W, lds, stream, a)) != hipSuccess) return e;
             if (pair_nofix()) return hipSuccess;  // diagnostics only: flagged chunks stay wrong
-            note_launch(CRLOT_K_PAIR_FIX, grid);
-            hipLaunchKernelGGL(kf, dim3(unsigned(grid)), dim3(64 * W), lds, stream, a);
-            return hipGetLastError();
+            return launch_kernel_plain(kf, CRLOT_K_PAIR_FIX, grid3, block3, lds, stream, a);
         }
     }
     FusedArgs b = a;
     b.fix_all = 1;
-    note_launch(CRLOT_K_PAIR_ALL, grid);
-    hipLaunchKernelGGL(kf, dim3(unsigned(grid)), dim3(64 * W), lds, stream, b);
-    return hipGetLastError();
+    return launch_kernel_plain(kf, CRLOT_K_PAIR_ALL, grid3, block3, lds, stream, b);
 }
 
 hipError_t launch_pair(int sh, const FusedArgs& a, int64_t waves, hipStream_t stream) {

@@ -21,7 +21,7 @@
 #include <cstdlib>
 
 #include "fft_pair15.h"
-#include "fused_common.h"
+#include "launch_common.h"
 
 namespace crlot {
 namespace fk {
@@ -257,27 +257,7 @@ hipError_t launch_pair30(const Geometry& g, const DevTables& t, const float* x, 
     if (!pair30_supported(g.n, g.h, g.ring_len) || !t.ptw || !t.pflags || F <= 0 ||
         n_streams <= 0 || T >= (int64_t(1) << 27) || out_len >= (int64_t(1) << 27))
         return hipErrorInvalidValue;
-    FusedArgs a;
-    a.t = t;
-    a.x = x;
-    a.y = y;
-    a.ld_x = ld_x;
-    a.ld_y = ld_y;
-    a.T = int(T);
-    a.out_len = int(out_len);
-    a.n_streams = n_streams;
-    a.F = int(F);
-    a.hop = g.h;
-    a.ring_blocks = g.ring_len / g.h;
-    a.pad = g.pad;
-    a.pad_mode = g.pad_mode;
-    a.inv_n = g.inv_n;
-    a.gain = g.gain;
-    // chunks: about two resident rounds of walks (two waves each), each >= 48 frames
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-        cus = 256;
+    FusedArgs a = fused_args(g, t, x, y, n_streams, T, ld_x, ld_y, F, out_len);
     constexpr size_t lds = p30_lds();
     // 3 waves/SIMD with the frames loaded at the top of each pair (no prefetch: 167
     // VGPRs) measured 121k / 207k Msamples/s at 1920/480 / 1920/960 against 115k /
@@ -290,22 +270,15 @@ hipError_t launch_pair30(const Geometry& g, const DevTables& t, const float* x, 
     }();
     const int wpe = t.gain || venv == 1 ? 2 : 3;
     const int64_t walks_per_cu = std::min<int64_t>(int64_t(160 * 1024 / lds), 2 * wpe);
-    const int64_t resident = int64_t(cus) * walks_per_cu;
-    const int64_t nc = chunks_or(std::max<int64_t>(1, std::min<int64_t>(F / 48, (2 * resident + n_streams - 1) / n_streams)), F);
-    a.M = int((F + nc - 1) / nc);
-    a.n_chunks = int((F + a.M - 1) / a.M);
+    // chunks: about two resident rounds of walks (two waves each), each >= 48 frames
+    choose_chunks_two_rounds(F, n_streams, device_cus() * walks_per_cu, F / 48, 0, a.n_chunks, a.M);
     const int64_t walks = int64_t(n_streams) * a.n_chunks;
     if (t.pflags_len < walks) return hipErrorInvalidValue;
     *n_chunks = a.n_chunks;
-    note_chunks(a.n_chunks);
     auto k = t.gain      ? k_pair30_hot<true, 2, true, false>
              : venv == 1 ? k_pair30_hot<false, 2, true, true>
                          : k_pair30_hot<false, 3, false, true>;
-    hipError_t e = set_lds(k, lds);
-    if (e != hipSuccess) return e;
-    note_launch(CRLOT_K_PAIR30, walks);
-    hipLaunchKernelGGL(k, dim3(unsigned(walks)), dim3(128), lds, stream, a);
-    return hipGetLastError();
+    return launch_kernel(k, CRLOT_K_PAIR30, walks, 128, lds, stream, a);
 }
 
 // the 960-point pair transform's tables (build_pair15_twiddles(960)), then [64]

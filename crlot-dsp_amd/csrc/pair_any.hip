@@ -30,7 +30,7 @@
 #include <vector>
 
 #include "fft_pair15.h"
-#include "fused_common.h"
+#include "launch_common.h"
 
 namespace crlot {
 namespace fk {
@@ -417,46 +417,18 @@ hipError_t launch_pair15(const Geometry& g, const DevTables& t, const float* x, 
         return !(e && e[0] == '0');
     }();
     const bool dpre = dpre_env && t.den_rden != nullptr && g.h <= 4 * (g.n / 15);
-    FusedArgs a;
-    a.t = t;
-    a.x = x;
-    a.y = y;
-    a.ld_x = ld_x;
-    a.ld_y = ld_y;
-    a.T = int(T);
-    a.out_len = int(out_len);
-    a.n_streams = n_streams;
-    a.F = int(F);
-    a.hop = g.h;
-    a.ring_blocks = g.ring_len / g.h;
-    a.pad = g.pad;
-    a.pad_mode = g.pad_mode;
-    a.inv_n = g.inv_n;
-    a.gain = g.gain;
-    // chunks: about two resident rounds of walkers, each >= 48 frames
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-        cus = 256;
+    FusedArgs a = fused_args(g, t, x, y, n_streams, T, ld_x, ld_y, F, out_len);
     const size_t lds = g.n == 960 ? p15_lds<64>(g.h, W, wreg) : p15_lds<32>(g.h, W, wreg);
     const int64_t wpc = std::min<int64_t>(W * int64_t(160 * 1024 / lds), 4 * kP15Shapes[v].wpe);  // waves per CU
-    const int64_t resident = int64_t(cus) * std::max<int64_t>(W, wpc);
+    // chunks: about two resident rounds of walkers, each >= 48 frames
     const int64_t units = (n_streams + halves - 1) / halves;
-    const int64_t n = chunks_or(std::max<int64_t>(1, std::min<int64_t>(F / 48, (2 * resident + units - 1) / units)), F);
-    a.M = int((F + n - 1) / n);
-    a.n_chunks = int((F + a.M - 1) / a.M);
+    choose_chunks_two_rounds(F, units, device_cus() * std::max<int64_t>(W, wpc), F / 48, 0, a.n_chunks, a.M);
     const int64_t waves = units * a.n_chunks;
     if (t.pflags_len < waves) return hipErrorInvalidValue;
     *n_chunks = a.n_chunks;
     *streams_per_walk = halves;
-    note_chunks(a.n_chunks);
     hipError_t e = hipSuccess;
-    auto go = [&](auto k, int w) {
-        if ((e = set_lds(k, lds)) != hipSuccess) return;
-        note_launch(CRLOT_K_PAIR15, (waves + w - 1) / w);
-        hipLaunchKernelGGL(k, dim3(unsigned((waves + w - 1) / w)), dim3(64 * w), lds, stream, a);
-        e = hipGetLastError();
-    };
+    auto go = [&](auto k, int w) { e = launch_kernel(k, CRLOT_K_PAIR15, (waves + w - 1) / w, 64 * w, lds, stream, a); };
     switch (v) {
         case 1: g.n == 960 ? go(k_pair15_hot<64, 2, true, 2>, 2) : go(k_pair15_hot<32, 2, true, 2>, 2); break;
         case 2: g.n == 960 ? go(k_pair15_hot<64, 4, false, 3>, 4) : go(k_pair15_hot<32, 4, false, 3>, 4); break;

@@ -27,7 +27,7 @@
 #include "fft_pair2k.h"
 #include "fft_pair4k.h"
 #include "fft_pair512.h"
-#include "fused_common.h"
+#include "launch_common.h"
 #include "ola_pair.h"
 
 namespace crlot {
@@ -427,13 +427,8 @@ template <typename G>
 hipError_t launch_wg_hot(int sh, const FusedArgs& a, int64_t grid, hipStream_t stream) {
     constexpr size_t lds = hot_lds<G>();
     if (CRLOT_HOT_PK && !a.t.pden2) return hipErrorInvalidValue;  // the block-pair divisor rows
-    auto go = [&](auto k) {
-        hipError_t e = set_lds(k, lds);
-        if (e != hipSuccess) return e;
-        note_launch(G::N == 4096 ? CRLOT_K_PAIR4K_HOT : CRLOT_K_PAIR2K_HOT, grid);
-        hipLaunchKernelGGL(k, dim3(unsigned(grid)), dim3(G::L), lds, stream, a);
-        return hipGetLastError();
-    };
+    constexpr int32_t id = G::N == 4096 ? CRLOT_K_PAIR4K_HOT : CRLOT_K_PAIR2K_HOT;
+    auto go = [&](auto k) { return launch_kernel(k, id, grid, G::L, lds, stream, a); };
     if constexpr (G::N == 2048) {  // H = 256 / 1024 spill at N = 2048: the two-regime walker runs those
         return sh == 4 && !a.t.gain ? go(k_pair_wg_hot<G, 4, 4>) : hipErrorInvalidValue;
     } else {
@@ -636,13 +631,7 @@ hipError_t launch_pair512_hot(int sh, const FusedArgs& a, int64_t waves, int w, 
     if (w != W || (CRLOT_HOT_PK && !a.t.pden2)) return hipErrorInvalidValue;
     const size_t lds = sizeof(dev::pc) * dev::kP512Buf * W;
     const int64_t grid = (waves + W - 1) / W;
-    auto go = [&](auto k) {
-        hipError_t e = set_lds(k, lds);
-        if (e != hipSuccess) return e;
-        note_launch(CRLOT_K_PAIR512_HOT, grid);
-        hipLaunchKernelGGL(k, dim3(unsigned(grid)), dim3(64 * W), lds, stream, a);
-        return hipGetLastError();
-    };
+    auto go = [&](auto k) { return launch_kernel(k, CRLOT_K_PAIR512_HOT, grid, 64 * W, lds, stream, a); };
     switch (sh) {
         case 2: return go(k_pair512_hot<2, 4, W>);
         case 4: return go(k_pair512_hot<4, 2, W>);

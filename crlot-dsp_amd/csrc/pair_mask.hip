@@ -31,7 +31,7 @@
 
 #include "fft_pair.h"
 #include "fft_pair512.h"
-#include "fused_common.h"
+#include "launch_common.h"
 
 namespace crlot {
 namespace fk {
@@ -530,19 +530,15 @@ __global__ __launch_bounds__(64 * kMW) void k_pair512_mask(const MaskWalkArgs ma
 
 template <int SH>
 hipError_t pair512_mask_sh(const MaskWalkArgs& a, int64_t grid, hipStream_t stream) {
-    constexpr int NB = 8 / SH;
-    hipLaunchKernelGGL((k_pair512_mask<SH, NB>), dim3(unsigned(grid)), dim3(64 * kMW), Mask512Lds::bytes, stream, a);
-    return hipGetLastError();
+    constexpr int NB = 8 / SH;  // (N = 512: the LDS request stays below the limit no attribute has to raise)
+    return launch_kernel_plain(k_pair512_mask<SH, NB>, CRLOT_K_PAIR_MASK, dim3(unsigned(grid)), dim3(64 * kMW),
+                               Mask512Lds::bytes, stream, a);
 }
 
 template <int SH>
 hipError_t pair_mask_sh(const MaskWalkArgs& a, int64_t grid, hipStream_t stream) {
     constexpr int NB = 16 / SH;
-    auto k = k_pair_mask<SH, NB>;
-    hipError_t e = set_lds(k, MaskLds::bytes);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k, dim3(unsigned(grid)), dim3(64 * kMW), MaskLds::bytes, stream, a);
-    return hipGetLastError();
+    return launch_kernel(k_pair_mask<SH, NB>, CRLOT_K_PAIR_MASK, grid, 64 * kMW, MaskLds::bytes, stream, a);
 }
 
 }  // namespace
@@ -580,7 +576,6 @@ hipError_t launch_pair_mask(int n, int h, const FusedArgs& f, const SpecMask& m,
     a.f = f;
     a.mask = m;
     const int64_t grid = (walkers + kMW - 1) / kMW;
-    note_launch(CRLOT_K_PAIR_MASK, grid);
     if (n == 512) {
         switch (h) {
             case 128: return pair512_mask_sh<2>(a, grid, stream);

@@ -24,7 +24,7 @@
 #include <vector>
 
 #include "fft_pairn.h"
-#include "fused_common.h"
+#include "launch_common.h"
 
 namespace crlot {
 namespace fk {
@@ -435,57 +435,28 @@ hipError_t launch_pairn(const Geometry& g, const DevTables& t, const float* x, f
     if (!pairn_supported(g.n, g.h, g.ring_len) || !t.ptw || !t.pflags || F <= 0 || n_streams <= 0 ||
         T >= (int64_t(1) << 27) || out_len >= (int64_t(1) << 27))
         return hipErrorInvalidValue;
-    FusedArgs a;
-    a.t = t;
-    a.x = x;
-    a.y = y;
-    a.ld_x = ld_x;
-    a.ld_y = ld_y;
-    a.T = int(T);
-    a.out_len = int(out_len);
-    a.n_streams = n_streams;
-    a.F = int(F);
-    a.hop = g.h;
-    a.ring_blocks = g.ring_len / g.h;
-    a.pad = g.pad;
-    a.pad_mode = g.pad_mode;
-    a.inv_n = g.inv_n;
-    a.gain = g.gain;
+    FusedArgs a = fused_args(g, t, x, y, n_streams, T, ld_x, ld_y, F, out_len);
     const int halves = pn_halves(g.n);
     const int walks = std::min(pn_walks(g.n, g.h), 4 * pn_wpe(pn_key(g.n)) / halves);  // per workgroup
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-        cus = 256;
     // chunks: about two resident rounds of walkers, each >= 48 frames
-    const int64_t resident = int64_t(cus) * walks;
     // (a forced chunking keeps a flag per wave within the F-per-stream flag rows)
-    const int64_t n = chunks_or(std::max<int64_t>(1, std::min<int64_t>(F / 48, (2 * resident + n_streams - 1) / n_streams)),
-                                std::max<int64_t>(1, F / halves));
-    a.M = int((F + n - 1) / n);
-    a.n_chunks = int((F + a.M - 1) / a.M);
+    choose_chunks_two_rounds(F, n_streams, int64_t(device_cus()) * walks, F / 48, 0, a.n_chunks, a.M,
+                             std::max<int64_t>(1, F / halves));
     const int64_t total = int64_t(n_streams) * a.n_chunks;  // walks
     if (t.pflags_len < total * halves) return hipErrorInvalidValue;
     *n_chunks = a.n_chunks * halves;  // flags per stream (one per wave)
-    note_chunks(a.n_chunks);
     const size_t lds = pn_tables(g.n) + size_t(walks) * pn_per_walk(g.n, g.h);
     hipError_t e = hipSuccess;
 #ifdef CRLOT_PN_DIT_EXPERIMENT
     if (pn_dit(g.n)) {  // 1764 = 2 x 882 on two waves (k_pairn_dit)
         auto k = t.gain ? k_pairn_dit<true> : k_pairn_dit<false>;
-        if ((e = set_lds(k, lds)) != hipSuccess) return e;
-        note_launch(CRLOT_K_PAIRN, (total + walks - 1) / walks);
-        hipLaunchKernelGGL(k, dim3(unsigned((total + walks - 1) / walks)), dim3(128 * walks), lds, stream, a);
-        return hipGetLastError();
+        return launch_kernel(k, CRLOT_K_PAIRN, (total + walks - 1) / walks, 128 * walks, lds, stream, a);
     }
 #endif
     pn_dispatch(pn_key(g.n), [&](auto nc) {
         constexpr int NN = decltype(nc)::value;
         auto k = t.gain ? k_pairn<NN, true> : k_pairn<NN, false>;
-        if ((e = set_lds(k, lds)) != hipSuccess) return;
-        note_launch(CRLOT_K_PAIRN, (total + walks - 1) / walks);
-        hipLaunchKernelGGL(k, dim3(unsigned((total + walks - 1) / walks)), dim3(64 * halves * walks), lds, stream, a);
-        e = hipGetLastError();
+        e = launch_kernel(k, CRLOT_K_PAIRN, (total + walks - 1) / walks, 64 * halves * walks, lds, stream, a);
     });
     return e;
 }

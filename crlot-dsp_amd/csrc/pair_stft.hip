@@ -29,7 +29,7 @@
 
 #include "fft_pair.h"
 #include "fft_pair512.h"
-#include "fused_common.h"
+#include "launch_common.h"
 #include "pair_spec_lds.h"
 
 namespace crlot {
@@ -651,12 +651,8 @@ __global__ __launch_bounds__(64 * kSW) void k_pair512_istft(const PairSpecArgs p
 }
 
 template <typename K>
-hipError_t launch_spec(K kernel, const PairSpecArgs& a, int64_t walkers, hipStream_t stream) {
-    hipError_t e = set_lds(kernel, SpecLds::bytes);
-    if (e != hipSuccess) return e;
-    const int64_t grid = (walkers + kSW - 1) / kSW;
-    hipLaunchKernelGGL(kernel, dim3(unsigned(grid)), dim3(64 * kSW), SpecLds::bytes, stream, a);
-    return hipGetLastError();
+hipError_t launch_spec(int32_t kind, K kernel, const PairSpecArgs& a, int64_t walkers, hipStream_t stream) {
+    return launch_kernel(kernel, kind, (walkers + kSW - 1) / kSW, 64 * kSW, SpecLds::bytes, stream, a);
 }
 
 }  // namespace
@@ -674,27 +670,26 @@ int pair_spec_walkers_per_cu(int n) {
     return v;
 }
 
+// (N = 512: the LDS request stays below the limit no attribute has to raise)
 template <typename K>
-hipError_t launch_spec512(K kernel, const PairSpecArgs& a, int64_t walkers, hipStream_t stream) {
+hipError_t launch_spec512(int32_t kind, K kernel, const PairSpecArgs& a, int64_t walkers, hipStream_t stream) {
     const int64_t grid = (walkers + kSW - 1) / kSW;
-    hipLaunchKernelGGL(kernel, dim3(unsigned(grid)), dim3(64 * kSW), Spec512Lds::bytes, stream, a);
-    return hipGetLastError();
+    return launch_kernel_plain(kernel, kind, dim3(unsigned(grid)), dim3(64 * kSW), Spec512Lds::bytes, stream, a);
 }
 
 hipError_t launch_pair_stft(int n, int h, const PairSpecArgs& a, int64_t walkers, hipStream_t stream) {
     if (n >= 2048) return launch_pairwg_stft(n, h, a, walkers, stream);
-    note_launch(CRLOT_K_PAIR_STFT, (walkers + kSW - 1) / kSW);
     if (n == 512) {
         switch (h) {
-            case 128: return launch_spec512(k_pair512_stft<2>, a, walkers, stream);
-            case 256: return launch_spec512(k_pair512_stft<4>, a, walkers, stream);
+            case 128: return launch_spec512(CRLOT_K_PAIR_STFT, k_pair512_stft<2>, a, walkers, stream);
+            case 256: return launch_spec512(CRLOT_K_PAIR_STFT, k_pair512_stft<4>, a, walkers, stream);
             default: return hipErrorInvalidValue;
         }
     }
     switch (h) {
-        case 128: return launch_spec(k_pair_stft<2>, a, walkers, stream);
-        case 256: return launch_spec(k_pair_stft<4>, a, walkers, stream);
-        case 512: return launch_spec(k_pair_stft<8>, a, walkers, stream);
+        case 128: return launch_spec(CRLOT_K_PAIR_STFT, k_pair_stft<2>, a, walkers, stream);
+        case 256: return launch_spec(CRLOT_K_PAIR_STFT, k_pair_stft<4>, a, walkers, stream);
+        case 512: return launch_spec(CRLOT_K_PAIR_STFT, k_pair_stft<8>, a, walkers, stream);
         default: return hipErrorInvalidValue;
     }
 }
@@ -702,9 +697,9 @@ hipError_t launch_pair_stft(int n, int h, const PairSpecArgs& a, int64_t walkers
 template <bool MASK>
 hipError_t pair_istft_m(int h, const PairSpecArgs& a, int64_t walkers, hipStream_t stream) {
     switch (h) {
-        case 128: return launch_spec(k_pair_istft<2, 8, MASK>, a, walkers, stream);
-        case 256: return launch_spec(k_pair_istft<4, 4, MASK>, a, walkers, stream);
-        case 512: return launch_spec(k_pair_istft<8, 2, MASK>, a, walkers, stream);
+        case 128: return launch_spec(CRLOT_K_PAIR_ISTFT, k_pair_istft<2, 8, MASK>, a, walkers, stream);
+        case 256: return launch_spec(CRLOT_K_PAIR_ISTFT, k_pair_istft<4, 4, MASK>, a, walkers, stream);
+        case 512: return launch_spec(CRLOT_K_PAIR_ISTFT, k_pair_istft<8, 2, MASK>, a, walkers, stream);
         default: return hipErrorInvalidValue;
     }
 }
@@ -712,15 +707,14 @@ hipError_t pair_istft_m(int h, const PairSpecArgs& a, int64_t walkers, hipStream
 template <bool MASK>
 hipError_t pair512_istft_m(int h, const PairSpecArgs& a, int64_t walkers, hipStream_t stream) {
     switch (h) {
-        case 128: return launch_spec512(k_pair512_istft<2, 4, MASK>, a, walkers, stream);
-        case 256: return launch_spec512(k_pair512_istft<4, 2, MASK>, a, walkers, stream);
+        case 128: return launch_spec512(CRLOT_K_PAIR_ISTFT, k_pair512_istft<2, 4, MASK>, a, walkers, stream);
+        case 256: return launch_spec512(CRLOT_K_PAIR_ISTFT, k_pair512_istft<4, 2, MASK>, a, walkers, stream);
         default: return hipErrorInvalidValue;
     }
 }
 
 hipError_t launch_pair_istft(int n, int h, const PairSpecArgs& a, int64_t walkers, hipStream_t stream) {
     if (n >= 2048) return launch_pairwg_istft(n, h, a, walkers, stream);
-    note_launch(CRLOT_K_PAIR_ISTFT, (walkers + kSW - 1) / kSW);
     if (n == 512)
         return a.mask.p ? pair512_istft_m<true>(h, a, walkers, stream) : pair512_istft_m<false>(h, a, walkers, stream);
     return a.mask.p ? pair_istft_m<true>(h, a, walkers, stream) : pair_istft_m<false>(h, a, walkers, stream);

@@ -32,7 +32,7 @@
 
 #include "fft_pair2k.h"
 #include "fft_pair4k.h"
-#include "fused_common.h"
+#include "launch_common.h"
 
 namespace crlot {
 namespace fk {
@@ -696,12 +696,8 @@ __global__ __launch_bounds__(G::L, 2) void k_pairwg_mask(const PairSpecArgs pa) 
 }
 
 template <typename G, typename K>
-hipError_t launch_wg(K kernel, const PairSpecArgs& a, int64_t walkers, hipStream_t stream) {
-    constexpr size_t lds = WgLds<G>::bytes;
-    hipError_t e = set_lds(kernel, lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kernel, dim3(unsigned(walkers)), dim3(G::L), lds, stream, a);
-    return hipGetLastError();
+hipError_t launch_wg(int32_t kind, K kernel, const PairSpecArgs& a, int64_t walkers, hipStream_t stream) {
+    return launch_kernel(kernel, kind, walkers, G::L, WgLds<G>::bytes, stream, a);
 }
 
 template <typename G, typename K>
@@ -729,27 +725,25 @@ int pair_wg_walkers_per_cu(int n) {
 
 hipError_t launch_pairwg_stft(int n, int h, const PairSpecArgs& a, int64_t walkers, hipStream_t stream) {
     if (!pair_wg_supported(n, h) || !a.f.t.ptw4 || !a.f.t.wa) return hipErrorInvalidValue;
-    note_launch(CRLOT_K_PAIR_STFT, walkers);
     auto go = [&](auto g) {
         using G = decltype(g);
         const int sh = h / G::L;
-        return sh == 2 ? launch_wg<G>(k_pairwg_stft<G, 2>, a, walkers, stream)
-                       : sh == 4 ? launch_wg<G>(k_pairwg_stft<G, 4>, a, walkers, stream)
-                                 : launch_wg<G>(k_pairwg_stft<G, 8>, a, walkers, stream);
+        return sh == 2 ? launch_wg<G>(CRLOT_K_PAIR_STFT, k_pairwg_stft<G, 2>, a, walkers, stream)
+                       : sh == 4 ? launch_wg<G>(CRLOT_K_PAIR_STFT, k_pairwg_stft<G, 4>, a, walkers, stream)
+                                 : launch_wg<G>(CRLOT_K_PAIR_STFT, k_pairwg_stft<G, 8>, a, walkers, stream);
     };
     return n == 4096 ? go(W4k{}) : go(W2k{});
 }
 
 template <typename G, bool MASK>
 hipError_t pairwg_istft_m(int sh, const PairSpecArgs& a, int64_t walkers, hipStream_t stream) {
-    return sh == 2   ? launch_wg<G>(k_pairwg_istft<G, 2, 8, MASK>, a, walkers, stream)
-           : sh == 4 ? launch_wg<G>(k_pairwg_istft<G, 4, 4, MASK>, a, walkers, stream)
-                     : launch_wg<G>(k_pairwg_istft<G, 8, 2, MASK>, a, walkers, stream);
+    return sh == 2   ? launch_wg<G>(CRLOT_K_PAIR_ISTFT, k_pairwg_istft<G, 2, 8, MASK>, a, walkers, stream)
+           : sh == 4 ? launch_wg<G>(CRLOT_K_PAIR_ISTFT, k_pairwg_istft<G, 4, 4, MASK>, a, walkers, stream)
+                     : launch_wg<G>(CRLOT_K_PAIR_ISTFT, k_pairwg_istft<G, 8, 2, MASK>, a, walkers, stream);
 }
 
 hipError_t launch_pairwg_istft(int n, int h, const PairSpecArgs& a, int64_t walkers, hipStream_t stream) {
     if (!pair_wg_supported(n, h) || !a.f.t.ptw4 || !a.f.t.pden4 || !a.f.t.wsn) return hipErrorInvalidValue;
-    note_launch(CRLOT_K_PAIR_ISTFT, walkers);
     const bool mask = a.mask.p != nullptr;
     if (n == 4096) {
         const int sh = h / 256;
@@ -762,15 +756,14 @@ hipError_t launch_pairwg_istft(int n, int h, const PairSpecArgs& a, int64_t walk
 
 template <typename G, bool GAIN>
 hipError_t pairwg_mask_g(int sh, const PairSpecArgs& a, int64_t walkers, hipStream_t stream) {
-    return sh == 2   ? launch_wg<G>(k_pairwg_mask<G, 2, 8, GAIN>, a, walkers, stream)
-           : sh == 4 ? launch_wg<G>(k_pairwg_mask<G, 4, 4, GAIN>, a, walkers, stream)
-                     : launch_wg<G>(k_pairwg_mask<G, 8, 2, GAIN>, a, walkers, stream);
+    return sh == 2   ? launch_wg<G>(CRLOT_K_PAIR_MASK, k_pairwg_mask<G, 2, 8, GAIN>, a, walkers, stream)
+           : sh == 4 ? launch_wg<G>(CRLOT_K_PAIR_MASK, k_pairwg_mask<G, 4, 4, GAIN>, a, walkers, stream)
+                     : launch_wg<G>(CRLOT_K_PAIR_MASK, k_pairwg_mask<G, 8, 2, GAIN>, a, walkers, stream);
 }
 
 hipError_t launch_pairwg_mask(int n, int h, const PairSpecArgs& a, int64_t walkers, hipStream_t stream) {
     if (!pair_wg_supported(n, h) || !a.mask.p || !a.f.t.ptw4 || !a.f.t.pden4 || !a.f.t.wsn)
         return hipErrorInvalidValue;
-    note_launch(CRLOT_K_PAIR_MASK, walkers);
     const bool gain = a.f.t.gain != nullptr;
     if (n == 4096) {
         const int sh = h / 256;

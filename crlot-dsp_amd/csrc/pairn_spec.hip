@@ -29,7 +29,7 @@
 #include <algorithm>
 
 #include "fft_pairn.h"
-#include "fused_common.h"
+#include "launch_common.h"
 
 namespace crlot {
 namespace fk {
@@ -516,29 +516,15 @@ __global__ __launch_bounds__(QN<K>::THREADS, 2) void k_pn_mask(const PairSpecArg
 template <int K, typename KF>
 hipError_t qn_launch(KF kernel, const PairSpecArgs& a, int64_t walks, int32_t kind, bool ring, hipStream_t stream) {
     using G = QN<K>;
-    const size_t lds = qn_lds<K>(a.f.hop, ring);
-    hipError_t e = set_lds(kernel, lds);
-    if (e != hipSuccess) return e;
-    const int64_t grid = (walks + G::WALKS - 1) / G::WALKS;
-    note_launch(kind, grid);
-    hipLaunchKernelGGL(kernel, dim3(unsigned(grid)), dim3(G::THREADS), lds, stream, a);
-    return hipGetLastError();
+    return launch_kernel(kernel, kind, (walks + G::WALKS - 1) / G::WALKS, G::THREADS, qn_lds<K>(a.f.hop, ring), stream,
+                         a);
 }
 
 // chunks: about two resident rounds of walks, each >= `min_m` frames, an even length
 int64_t qn_chunks(FusedArgs& f, int64_t F, int n_streams, int64_t min_m) {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-        cus = 256;
-    const int64_t resident = int64_t(cus) * 8, S = std::max(1, n_streams);  // (walks a CU holds, about)
-    int64_t c = std::max<int64_t>(1, std::min<int64_t>(F / min_m, (2 * resident + S - 1) / S));
-    c = chunks_or(c, F);
-    int64_t m = (F + c - 1) / c;
-    m += m & 1;
-    f.M = int(m);
-    f.n_chunks = int((F + m - 1) / m);
-    note_chunks(f.n_chunks);
+    const int64_t S = std::max(1, n_streams);
+    const int64_t resident = int64_t(device_cus()) * 8;  // (walks a CU holds, about)
+    choose_chunks_two_rounds(F, S, resident, F / min_m, kChunkEven, f.n_chunks, f.M);
     return S * f.n_chunks;
 }
 
@@ -572,19 +558,7 @@ hipError_t launch_pairn_stft(const Geometry& g, const DevTables& t, const float*
     if (!pairn_spec_supported(g.n, g.h, g.ring_len) || F <= 0 || n_streams <= 0 || !t.ptwn || !t.wa ||
         T >= (int64_t(1) << 27))
         return hipErrorInvalidValue;
-    fk::PairSpecArgs a{};
-    a.f.t = t;
-    a.f.x = x;
-    a.f.ld_x = ld_x;
-    a.f.T = int(T);
-    a.f.n_streams = n_streams;
-    a.f.F = int(F);
-    a.f.hop = g.h;
-    a.f.pad = g.pad;
-    a.f.pad_mode = g.pad_mode;
-    a.spec = spec;
-    a.ld_spec = ld_spec;
-    a.ld_frame = ld_frame;
+    fk::PairSpecArgs a = fk::pair_stft_args(g, t, x, n_streams, T, ld_x, F, spec, ld_spec, ld_frame);
     const int64_t waves = fk::qn_chunks(a.f, F, n_streams, 32);
     hipError_t e = hipErrorInvalidValue;
     fk::qn_dispatch(g.n, [&](auto kc) {
@@ -601,21 +575,7 @@ hipError_t launch_pairn_istft(const Geometry& g, const DevTables& t, const SpecM
     if (!pairn_spec_supported(g.n, g.h, g.ring_len) || F <= 0 || n_streams <= 0 || !t.ptwn || !t.ws || !t.den ||
         F * g.h + g.n >= (int64_t(1) << 27))
         return hipErrorInvalidValue;
-    fk::PairSpecArgs a{};
-    a.f.t = t;
-    a.f.y = y;
-    a.f.ld_y = ld_y;
-    a.f.out_len = int(F * g.h);
-    a.f.n_streams = n_streams;
-    a.f.F = int(F);
-    a.f.hop = g.h;
-    a.f.ring_blocks = g.ring_len / g.h;
-    a.f.inv_n = g.inv_n;
-    a.f.gain = g.gain;
-    a.sin = spec;
-    a.ld_spec = ld_spec;
-    a.ld_frame = ld_frame;
-    a.mask = m;
+    fk::PairSpecArgs a = fk::pair_istft_args(g, t, m, spec, ld_spec, ld_frame, y, n_streams, F, ld_y);
     const int64_t waves = fk::qn_chunks(a.f, F, n_streams, 48);
     hipError_t e = hipErrorInvalidValue;
     fk::qn_dispatch(g.n, [&](auto kc) {
@@ -633,23 +593,7 @@ hipError_t launch_pairn_masked(const Geometry& g, const DevTables& t, const Spec
     if (!pairn_spec_supported(g.n, g.h, g.ring_len) || F <= 0 || n_streams <= 0 || !m.p || !t.ptwn || !t.wa ||
         !t.ws || !t.den || T >= (int64_t(1) << 27) || out_len + g.n >= (int64_t(1) << 27))
         return hipErrorInvalidValue;
-    fk::PairSpecArgs a{};
-    a.f.t = t;
-    a.f.x = x;
-    a.f.y = y;
-    a.f.ld_x = ld_x;
-    a.f.ld_y = ld_y;
-    a.f.T = int(T);
-    a.f.out_len = int(out_len);
-    a.f.n_streams = n_streams;
-    a.f.F = int(F);
-    a.f.hop = g.h;
-    a.f.ring_blocks = g.ring_len / g.h;
-    a.f.pad = g.pad;
-    a.f.pad_mode = g.pad_mode;
-    a.f.inv_n = g.inv_n;
-    a.f.gain = g.gain;
-    a.mask = m;
+    fk::PairSpecArgs a = fk::pair_masked_args(g, t, m, x, y, n_streams, T, ld_x, ld_y, F, out_len);
     const int64_t waves = fk::qn_chunks(a.f, F, n_streams, 48);
     hipError_t e = hipErrorInvalidValue;
     fk::qn_dispatch(g.n, [&](auto kc) {

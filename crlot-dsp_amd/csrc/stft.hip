@@ -32,7 +32,7 @@
 #include <cstdint>
 
 #include "fft_wave.h"
-#include "fused_common.h"
+#include "launch_common.h"
 #include "kernels.h"
 #include "stft_walk.h"
 
@@ -699,14 +699,11 @@ size_t istft_wg_lds() {
 template <typename K>
 hipError_t launch_walk(K kernel, int32_t id, int threads, int per_block, size_t lds, int min_m, StftArgs& a,
                        hipStream_t stream) {
-    hipError_t e = set_lds(kernel, lds);
+    hipError_t e = set_lds(kernel, lds);  // (before the occupancy query, which needs the raised limit)
     if (e != hipSuccess) return e;
     pick_chunks(a.F, a.n_streams, resident_walkers(kernel, threads, lds, per_block), min_m, a.n_chunks, a.M);
-    note_chunks(a.n_chunks);
     const int64_t grid = (int64_t(a.n_streams) * a.n_chunks + per_block - 1) / per_block;
-    note_launch(id, grid);
-    hipLaunchKernelGGL(kernel, dim3(unsigned(grid)), dim3(threads), lds, stream, a);
-    return hipGetLastError();
+    return launch_kernel_plain(kernel, id, dim3(unsigned(grid)), dim3(threads), lds, stream, a);
 }
 
 template <int E, int S, bool XIN>
@@ -825,20 +822,16 @@ hipError_t launch_frames_windowed(const Geometry& g, const DevTables& t, const f
                                   int64_t ld_x, int64_t F, float* frames, hipStream_t stream) {
     const int64_t rows = int64_t(n_streams) * F;
     if (rows <= 0 || rows > INT32_MAX) return hipErrorInvalidValue;
-    note_launch(CRLOT_K_FRAMES_W, rows);
-    hipLaunchKernelGGL(k_frames_w, dim3(unsigned(rows)), dim3(256), 0, stream, x, ld_x, T, t.wa, frames, F, g.n,
-                       g.h, g.pad, g.pad_mode);
-    return hipGetLastError();
+    return fk::launch_kernel_plain(k_frames_w, CRLOT_K_FRAMES_W, dim3(unsigned(rows)), dim3(256), 0, stream, x, ld_x, T,
+                                   t.wa, frames, F, g.n, g.h, g.pad, g.pad_mode);
 }
 
 hipError_t launch_spec_step(const DevTables& t, const SpecMask& m, const float* spec, int64_t ld_spec,
                             int64_t ld_frame, float* out, int n_streams, int64_t F, int bins, hipStream_t stream) {
     const int64_t rows = int64_t(n_streams) * F;
     if (rows <= 0 || rows > INT32_MAX) return hipErrorInvalidValue;
-    note_launch(CRLOT_K_SPEC_STEP, rows);
-    hipLaunchKernelGGL(k_spec_step, dim3(unsigned(rows)), dim3(256), 0, stream, spec, ld_spec, ld_frame, out, F,
-                       bins, t.gain, m);
-    return hipGetLastError();
+    return fk::launch_kernel_plain(k_spec_step, CRLOT_K_SPEC_STEP, dim3(unsigned(rows)), dim3(256), 0, stream, spec,
+                                   ld_spec, ld_frame, out, F, bins, t.gain, m);
 }
 
 }  // namespace crlot

@@ -1,16 +1,17 @@
 // stft_walk.h -- the pieces of K_stft's walk (stft.hip) that the feature walkers
 // (feat.hip) run unchanged: the kernel arguments, the frame loads with the
 // plan's padding, kiss_fftr's split of one bin, the per-size configuration and
-// the chunk chooser.  One definition, so the spectrum a feature kernel squares
-// is bit for bit the one crlot_stft stores.
+// the chunk chooser (a policy of the host launch layer, launch_common.h).  One
+// definition, so the spectrum a feature kernel squares is bit for bit the one
+// crlot_stft stores.
 #pragma once
 
 #include <algorithm>
 #include <cstdint>
 
 #include "fft_wave.h"
-#include "fused_common.h"
 #include "kernels.h"
+#include "launch_common.h"
 
 namespace crlot {
 namespace sw {
@@ -109,30 +110,12 @@ size_t stft_lds() {
     return sizeof(cf) * (C::TW + (C::TL ? C::P : 0) + kW * C::P);
 }
 
-inline int cus() {
-    static const int v = [] {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-            n = 256;
-        return n;
-    }();
-    return v;
-}
-
 // Chunks per stream: enough walkers for two resident rounds of the device
 // (`resident` walkers at once), chunks of about 128 frames while the grid stays
 // that deep, at least `min_m` frames each (the istft walk recomputes NB-1
 // warm-up frames per chunk); the plan's chunk knob overrides.
 inline void pick_chunks(int64_t F, int n_streams, int64_t resident, int min_m, int& n_chunks, int& m) {
-    const int64_t S = std::max(1, n_streams);
-    int64_t n = (F + 127) / 128;
-    n = std::max<int64_t>(n, (2 * std::max<int64_t>(1, resident) + S - 1) / S);
-    n = std::min<int64_t>(n, std::max<int64_t>(1, F / std::max(1, min_m)));
-    if (const int64_t c = chunks_or(0, F); c > 0) n = c;
-    n = std::max<int64_t>(1, std::min<int64_t>(n, F));
-    m = int((F + n - 1) / n);
-    n_chunks = int((F + m - 1) / m);
+    choose_chunks_two_rounds(F, n_streams, resident, F / std::max(1, min_m), kChunkFill128, n_chunks, m);
 }
 
 // walkers the device holds at once: workgroups per CU x walkers per workgroup x CUs
@@ -143,7 +126,7 @@ int64_t resident_walkers(K kernel, int threads, size_t lds, int walkers_per_bloc
             hipSuccess ||
         nb <= 0)
         nb = 1;
-    return int64_t(nb) * walkers_per_block * cus();
+    return int64_t(nb) * walkers_per_block * device_cus();
 }
 
 inline StftArgs base_args(const Geometry& g, const DevTables& t, int n_streams, int64_t F) {

@@ -30,7 +30,7 @@
 
 #include "fft_any.h"
 #include "fft_wave.h"
-#include "fused_common.h"
+#include "launch_common.h"
 #include "kernels.h"
 #include "stream_common.h"
 
@@ -77,10 +77,7 @@ __global__ __launch_bounds__(512) void k_stream_any_spec(const StreamAnySpecArgs
 // ------------------------------------------------------------------ dispatch
 template <typename K>
 hipError_t launch_spec(K k, size_t lds, const StreamSpecArgs& g, hipStream_t stream) {
-    hipError_t e = set_lds(k, lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k, dim3(unsigned((g.s.channels + kWaves - 1) / kWaves)), dim3(kBlock), lds, stream, g);
-    return hipGetLastError();
+    return launch_kernel(k, kNoRecord, (g.s.channels + kWaves - 1) / kWaves, kBlock, lds, stream, g);
 }
 
 template <int E, int S>
@@ -132,11 +129,8 @@ hipError_t spec_dispatch(const Geometry& g, int mode, const StreamSpecArgs& a, h
 
 template <typename K>
 hipError_t launch_any_spec(K k, size_t lds, const StreamAnySpecArgs& g, hipStream_t stream) {
-    hipError_t e = set_lds(k, lds);
-    if (e != hipSuccess) return e;
     const int w = g.f.a.waves_per_block;
-    hipLaunchKernelGGL(k, dim3(unsigned((g.f.channels + w - 1) / w)), dim3(64 * w), lds, stream, g);
-    return hipGetLastError();
+    return launch_kernel(k, kNoRecord, (g.f.channels + w - 1) / w, 64 * w, lds, stream, g);
 }
 
 hipError_t any_dispatch(int mode, size_t lds, const StreamAnySpecArgs& g, hipStream_t stream) {
