@@ -82,6 +82,26 @@ struct PairLds {
 #define CRLOT_PAIR_OSCREEN 1  // output-sanitize screen (v_min3 over |v|) off the window-edge registers, the exact test only where it fails
 #endif
 #define CRLOT_PAIR_PKA ((CRLOT_PAIR_PK2 >> 1) & 1)
+// Progress-keyed wave priority of the hot walker at H = 256 (scheduling only, no
+// output bit moves).  VALU issue on a SIMD goes by priority, then age, so of the
+// three walks on a SIMD the oldest runs ahead and the youngest finishes last; at
+// the end of the launch's last resident round nothing replaces a finished walk
+// and the late ones run two, then one to a SIMD (19 % of all wave-slot time,
+// DESIGN.md section 5).  Once per trip of the main loop the walk lowers its
+// priority by how far it has got: 3 below T1/64 of its chunk's M frames (equal
+// for every walk of a launch), 2 below T2/64, 1 below T3/64, then 0.  A walk that
+// is behind its SIMD's other walks leads until it has caught up, a new walk
+// starts at the top (its table staging included), and the steps narrow towards
+// the end, where the walks have to meet.  0 builds the walk without it
+// (priority by age alone).  Thresholds measured: DESIGN.md section 5.
+#ifndef CRLOT_PAIR_PRIO
+#define CRLOT_PAIR_PRIO 1
+#endif
+#ifndef CRLOT_PAIR_PRIO_T1
+#define CRLOT_PAIR_PRIO_T1 32
+#define CRLOT_PAIR_PRIO_T2 52
+#define CRLOT_PAIR_PRIO_T3 60
+#endif
 #ifndef CRLOT_PAIR_MIN_WAVES
 #define CRLOT_PAIR_MIN_WAVES (CRLOT_PAIR_REG_TW ? 3 : 4)
 #endif
@@ -117,6 +137,29 @@ struct PairRot {
 template <int SH>
 constexpr bool kPairFoldWs = SH != 2;
 
+// CRLOT_PAIR_PRIO applies at H = 256 on planar rows.  At H = 512 the branch grows
+// the walk's spills (2 -> 12 VGPRs) and measured -7.5 %, at H = 128 it measured
+// +0.1 % (inside the controls' spread); the interleaved walk was not measured.
+template <int SH, bool ILV>
+constexpr bool kPairPrio = CRLOT_PAIR_PRIO != 0 && SH == 4 && !ILV;
+
+#ifdef CRLOT_PAIR_TRACE
+// `make variant DEFS=-DCRLOT_PAIR_TRACE` only (tools/probes/wave_timeline.py): every
+// hot walk's start and end (100 MHz s_memrealtime), HW_ID and XCC_ID, read back
+// through crlot_debug_pair_trace.  Never in the release library.
+__device__ uint32_t g_pair_trace[1 << 16][4];
+#endif
+
+// s_setprio takes an immediate: a four-way scalar branch on a wave-uniform value
+__device__ __forceinline__ void pair_set_prio(uint32_t p) {
+    switch (p & 3u) {
+        case 0: __builtin_amdgcn_s_setprio(0); break;
+        case 1: __builtin_amdgcn_s_setprio(1); break;
+        case 2: __builtin_amdgcn_s_setprio(2); break;
+        default: __builtin_amdgcn_s_setprio(3); break;
+    }
+}
+
 template <int SH, int NB, int W, bool ILV, bool HAS_GAIN>
 __global__ __launch_bounds__(64 * W, CRLOT_PAIR_MIN_WAVES) void k_stft_ola_pair(const FusedArgs a) {
     constexpr int E = 16, N = 1024, H = 64 * SH;
@@ -128,6 +171,13 @@ __global__ __launch_bounds__(64 * W, CRLOT_PAIR_MIN_WAVES) void k_stft_ola_pair(
     dev::pc* t2s = reinterpret_cast<dev::pc*>(smem + PairLds<W>::t2);
     float* wa4 = reinterpret_cast<float*>(smem + PairLds<W>::wa);
     float* ws4 = reinterpret_cast<float*>(smem + PairLds<W>::ws);
+    // (CRLOT_PAIR_PRIO: a new walk starts at the top, so the table staging of a
+    // workgroup that joins two half-done walks on its SIMDs is not starved)
+    constexpr bool prio_on = kPairPrio<SH, ILV>;
+    if constexpr (prio_on) __builtin_amdgcn_s_setprio(3);
+#ifdef CRLOT_PAIR_TRACE
+    const uint32_t trace_t0 = uint32_t(__builtin_amdgcn_s_memrealtime());
+#endif
     {
         const dev::pc* g1 = reinterpret_cast<const dev::pc*>(a.t.ptw);
         for (int i = threadIdx.x; i < 15 * 64 + 3 * 16; i += 64 * W) t1[i] = g1[i];  // t1 | t2
@@ -154,6 +204,10 @@ __global__ __launch_bounds__(64 * W, CRLOT_PAIR_MIN_WAVES) void k_stft_ola_pair(
     const dev::pc* const tw1 = t1;
     const dev::pc* const tw2 = t2;
 #endif
+    // progress of the walk in 64ths: done * prio_rate >> 20 = floor(64 done / M)
+    // without a division in the loop (done < M + NB, so the product fits 32 bits
+    // for every M >= 1; chunks longer than 2^26 frames stay at the top)
+    const uint32_t prio_rate = prio_on ? (64u << 20) / uint32_t(max(a.M, 1)) : 0u;
     // spectral gain (the spectral hook, the two-regime walker's operation): once
     // every wave holds its twiddles in registers, the per-bin gain [N] replaces
     // the twiddle table in LDS (no room for both beside three workgroups per CU)
@@ -438,6 +492,10 @@ __global__ __launch_bounds__(64 * W, CRLOT_PAIR_MIN_WAVES) void k_stft_ola_pair(
 #endif
     };
     for (int k = fs; k < f1; k += 2 * U) {
+        if constexpr (prio_on) {  // (SALU only: k, fs and M are wave-uniform)
+            const uint32_t p = (uint32_t(k - fs) * prio_rate) >> 20;
+            pair_set_prio(3u - (p >= CRLOT_PAIR_PRIO_T1) - (p >= CRLOT_PAIR_PRIO_T2) - (p >= CRLOT_PAIR_PRIO_T3));
+        }
         step(std::integral_constant<int, 0>(), k);
         if constexpr (U > 1) {
             if (k + 2 >= f1) break;
@@ -472,6 +530,14 @@ __global__ __launch_bounds__(64 * W, CRLOT_PAIR_MIN_WAVES) void k_stft_ola_pair(
         a.t.pflags[gw] = fa;
         a.t.pflags[gw + a.n_streams * a.n_chunks] = fb;
     }
+#ifdef CRLOT_PAIR_TRACE
+    if (lane == 0 && gw < (1 << 16)) {
+        g_pair_trace[gw][0] = trace_t0;
+        g_pair_trace[gw][1] = uint32_t(__builtin_amdgcn_s_memrealtime());
+        g_pair_trace[gw][2] = __builtin_amdgcn_s_getreg((31 << 11) | 4);   // HW_ID
+        g_pair_trace[gw][3] = __builtin_amdgcn_s_getreg((31 << 11) | 20);  // XCC_ID
+    }
+#endif
 }
 #undef CRLOT_ACC
 #undef XR
@@ -849,4 +915,12 @@ std::vector<float> build_pair_twiddles() {
 
 
 }  // namespace crlot
+
+#ifdef CRLOT_PAIR_TRACE
+// (variant builds only: the release library's export list does not have it)
+extern "C" int crlot_debug_pair_trace(void* dst, int64_t bytes) {
+    const size_t n = std::min(size_t(bytes), sizeof(crlot::fk::g_pair_trace));
+    return int(hipMemcpyFromSymbol(dst, HIP_SYMBOL(crlot::fk::g_pair_trace), n));
+}
+#endif
 

@@ -1,6 +1,8 @@
 """Per-wave timeline of K_pair from a CRLOT_PAIR_TRACE build (variants/libcrlot_dsp_trace.so):
 wave start/end (100 MHz s_memrealtime) and hardware ids; prints the duration spread,
-the mean resident waves per SIMD and how long each CU idles between its workgroups."""
+the mean resident waves per SIMD and how long each CU idles between its workgroups.
+TL_LIB names another trace variant, TL_DUMP a .npy file for the raw records
+(start, end, HW_ID, XCC_ID per walk), TL_WG_WAVES the waves per workgroup."""
 import ctypes as C
 import json
 import os
@@ -8,17 +10,18 @@ import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
-lib = os.path.join(ROOT, "crlot-dsp_amd", "variants", "libcrlot_dsp_trace.so")
+lib = os.environ.get("TL_LIB") or os.path.join(ROOT, "crlot-dsp_amd", "variants", "libcrlot_dsp_trace.so")
 os.environ["CRLOT_LIB"] = lib
 from __graft_entry__ import load_pkg  # noqa: E402
 
 pkg = load_pkg()
 L = pkg.lib()
 S, T = int(os.environ.get("TL_S", 1024)), 480000
+W = int(os.environ.get("TL_WG_WAVES", 4))  # waves per workgroup (CRLOT_PAIR_WAVES)
 plan = pkg.Plan(frame_size=1024, hop_size=256)
 g = torch.Generator(device="cuda").manual_seed(3)
 x = (torch.rand((S, T), generator=g, device="cuda") * 2 - 1) * 0.5
@@ -30,6 +33,8 @@ buf = np.zeros((1 << 16, 4), np.uint32)
 L.crlot_debug_pair_trace.argtypes = [C.c_void_p, C.c_int64]
 assert L.crlot_debug_pair_trace(buf.ctypes.data, buf.nbytes) == 0
 n = int(np.count_nonzero(buf[:, 1]))
+if os.environ.get("TL_DUMP"):  # the raw records, for a closer look offline
+    np.save(os.environ["TL_DUMP"], buf[:n])
 t = buf[:n].astype(np.int64)
 t0 = t[:, 0].min()
 st, en = t[:, 0] - t0, t[:, 1] - t0
@@ -51,12 +56,12 @@ for c in np.unique(cuid):
     s_, e_ = st[m], en[m]
     order = np.argsort(s_)
     s_, e_ = s_[order], e_[order]
-    # group waves into workgroups by start time clusters (16 per WG)
-    for i in range(0, len(s_), 16):
-        grp_e = e_[i:i + 16]
+    # group waves into workgroups by start time clusters (W per WG)
+    for i in range(0, len(s_), W):
+        grp_e = e_[i:i + W]
         wg_spread.append((grp_e.max() - grp_e.min()) / 100.0)
-        if i + 16 < len(s_):
-            gaps.append((s_[i + 16:i + 32].min() - grp_e.max()) / 100.0)
+        if i + W < len(s_):
+            gaps.append((s_[i + W:i + 2 * W].min() - grp_e.max()) / 100.0)
 out["wg_end_spread_us_med"] = float(np.median(wg_spread))
 out["wg_end_spread_us_max"] = float(np.max(wg_spread))
 out["gap_between_wgs_us_med"] = float(np.median(gaps)) if gaps else None
