@@ -168,6 +168,7 @@ def lib():
         "crlot_stream_stft_hop": ([vp, vp, vp, i64, C.POINTER(i32), vp], C.c_int),
         "crlot_stream_istft_hop": ([vp, vp, i64, vp, i64, vp, vp], C.c_int),
         "crlot_stream_push_hop_masked": ([vp, vp, vp, i64, vp, C.POINTER(i32), vp], C.c_int),
+        "crlot_stream_features_hop": ([vp, vp, vp, vp, i64, vp, i64, C.POINTER(i32), vp], C.c_int),
         "crlot_stream_set_layout": ([vp, i32], C.c_int),
         "crlot_stream_rt_create": ([vp, i32, i32, i32, C.POINTER(vp)], C.c_int),
         "crlot_stream_rt_destroy": ([vp], None),
@@ -739,6 +740,27 @@ def _spectrogram_out_layout(shape, strides, dtype: str, device_index, S: int, F:
     return ld_out, ld_frame
 
 
+def _features_hop_out_layout(shape, strides, dtype: str, device_index, channels: int, n_out: int,
+                             same_plan: bool = True):
+    """The same for Stream.features_hop's output: (channels, n_out) float32 on the
+    device, rows contiguous and at least n_out apart, the features object built on
+    the stream's plan (same_plan).  Returns ld_feat."""
+    if not same_plan:
+        raise ValueError("features was created on another plan than the stream's")
+    if dtype != "float32":
+        raise ValueError(f"out must be float32, not {dtype}")
+    if device_index is None:
+        raise ValueError("out must be a device tensor")
+    if tuple(int(v) for v in shape) != (channels, n_out) or len(strides) != 2:
+        raise ValueError(f"out must be ({channels}, {n_out})")
+    if n_out > 1 and int(strides[1]) != 1:
+        raise ValueError("out must have contiguous rows")
+    ld_feat = int(strides[0]) if channels > 1 else n_out  # (a size-1 dim's stride is meaningless)
+    if ld_feat < n_out:
+        raise ValueError("out rows overlap: ld_feat < n_out")
+    return ld_feat
+
+
 def _tensor_layout(t):
     return (tuple(t.shape), tuple(t.stride()), str(t.dtype).replace("torch.", ""),
             (t.device.index if t.device.index is not None else 0) if t.is_cuda else None)
@@ -1133,6 +1155,33 @@ class Stream:
         _check(lib().crlot_stream_stft_hop(self._h, hop.data_ptr(), spec.data_ptr(), ld, C.byref(em), s),
                "crlot_stream_stft_hop")
         return spec, em.value
+
+    def features_hop(self, features, hop, out=None, spec=None, stream: int | None = None) -> tuple:
+        """stft_hop with the features computed where the spectrum row would be stored
+        (crlot_stream_features_hop).  features: a Features of this stream's plan; hop as
+        push_hop's.  Returns (out, emitted): out a (channels, n_out) float32 tensor (rows
+        may be padded) holding, when emitted is 1, the features of the frame this hop
+        completes, else untouched.  spec (optional, (channels, N/2+1) complex64) also
+        receives stft_hop's row from the same launch.  Shares stft_hop's hop counter."""
+        torch = _torch()
+        hop = self._hop_arg(hop)
+        if not isinstance(features, Features):
+            raise ValueError("features must be a Features object")
+        if out is None:
+            out = torch.empty((self.channels, features.n_out), dtype=torch.float32, device=hop.device)
+        if not torch.is_tensor(out):
+            raise ValueError("out must be a float32 device tensor")
+        ld_feat = _features_hop_out_layout(*_tensor_layout(out), self.channels, features.n_out,
+                                           features.plan is self.plan)
+        sp, ld_spec = None, 0
+        if spec is not None:
+            ld_spec = self._spec_arg(spec)
+            sp = spec.data_ptr()
+        em = C.c_int32()
+        s = _stream_handle(hop) if stream is None else stream
+        _check(lib().crlot_stream_features_hop(self._h, features._h, hop.data_ptr(), out.data_ptr(), ld_feat, sp,
+                                               ld_spec, C.byref(em), s), "crlot_stream_features_hop")
+        return out, em.value
 
     def istft_hop(self, spec, mask=None, out=None, stream: int | None = None):
         """The synthesis half: spec (channels, N/2+1) complex64 -> the plan's gain, then

@@ -1356,6 +1356,22 @@ struct crlot_features {
 namespace {
 // the staged form's workspace per slice of streams (one stream's worth if that is more)
 constexpr int64_t kFeatWorkspaceCap = int64_t(256) << 20;
+
+// what the feature kernels take from the object, for one output placement
+crlot::FeatDev feat_dev(const crlot_features* f, float* d_out, int64_t ld_out, int64_t ld_frame) {
+    crlot::FeatDev fd{};
+    fd.out = d_out;
+    fd.ld_out = ld_out;
+    fd.ld_frame = ld_frame;
+    fd.bands = f->d_bands;
+    fd.w = f->d_w;
+    fd.n_bands = f->desc.n_bands;
+    fd.kind = f->desc.kind;
+    fd.log = f->desc.log;
+    fd.floor = f->desc.floor;
+    fd.n_w = f->n_w;
+    return fd;
+}
 }  // namespace
 
 extern "C" {
@@ -1446,17 +1462,7 @@ int crlot_spectrogram(crlot_features* f, const float* d_x, float* d_out, int32_t
     hipStream_t s = static_cast<hipStream_t>(stream);
     std::lock_guard<std::mutex> lk(p->mu);
     const crlot::DevTables t = tables(p);
-    crlot::FeatDev fd{};
-    fd.out = d_out;
-    fd.ld_out = ld_out;
-    fd.ld_frame = ld_frame;
-    fd.bands = f->d_bands;
-    fd.w = f->d_w;
-    fd.n_bands = f->desc.n_bands;
-    fd.kind = f->desc.kind;
-    fd.log = f->desc.log;
-    fd.floor = f->desc.floor;
-    fd.n_w = f->n_w;
+    crlot::FeatDev fd = feat_dev(f, d_out, ld_out, ld_frame);
     const RouteKind route = stft_route(p, t, d_x, T, ld_x, n_streams, F).kind;
     if (route == RouteKind::kPair && crlot::pair_feat_supported(p->geo.n, p->geo.h)) {
         const hipError_t e = crlot::launch_pair_feat(p->geo, t, fd, d_x, n_streams, T, ld_x, F, s);
@@ -2108,6 +2114,33 @@ int crlot_stream_stft_hop(crlot_stream* st, const float* d_in, float* d_spec, in
     hipError_t e = crlot::launch_stream_stft_hop(p->geo, tables(p), p->d_twany, st->any, d_in, ld, inc, d_spec,
                                                  ld_spec, st->d_hist, st->channels, st->q, k,
                                                  static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(e, "stream kernel launch");
+    if (emitted) *emitted = k >= 0 ? 1 : 0;
+    st->q += 1;
+    return CRLOT_OK;
+}
+
+int crlot_stream_features_hop(crlot_stream* st, const crlot_features* f, const float* d_in, float* d_feat,
+                              int64_t ld_feat, float* d_spec, int64_t ld_spec, int32_t* emitted, void* stream) {
+    if (emitted) *emitted = 0;
+    if (!st) return fail(CRLOT_EINVAL, "null stream");
+    if (!f) return fail(CRLOT_EINVAL, "null features object");
+    if (!d_in || !d_feat) return fail(CRLOT_EINVAL, "null buffer");
+    if (f->plan != st->plan) return fail(CRLOT_EINVAL, "the features object was created on another plan");
+    if (ld_feat < f->n_out) return fail(CRLOT_EINVAL, "ld_feat is smaller than n_out");
+    if (d_spec) {
+        if (int rc = check_spec_row(st, d_spec, ld_spec)) return rc;
+    }
+    if (int rc = stream_enter(st, 2)) return rc;
+    crlot_plan* p = st->plan;
+    DeviceGuard g(p->device);
+    const int64_t C = st->channels, H = p->geo.h;
+    const int64_t ld = st->interleaved ? 1 : H, inc = st->interleaved ? C : 1;
+    const int64_t k = stream_frame_of_hop(st, st->q);
+    hipError_t e = crlot::launch_stream_features_hop(p->geo, tables(p), p->d_twany, st->any,
+                                                     feat_dev(f, d_feat, ld_feat, 0), d_in, ld, inc, d_spec,
+                                                     d_spec ? ld_spec : 0, st->d_hist, st->channels, st->q, k,
+                                                     static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return hip_fail(e, "stream kernel launch");
     if (emitted) *emitted = k >= 0 ? 1 : 0;
     st->q += 1;

@@ -221,10 +221,11 @@ __device__ __forceinline__ cf rmerge(const cf& xk, const cf& xpk, const cf& w, i
 // k <= P.  st: exp(-i pi (k/P + 1/2)), k < P.  HAS_MASK: a real mask row (P + 1
 // floats) multiplies X after the gain, (X * gain) * mask on re and im each.
 // MERGE = false: the split alone (dst untouched; spec may be a row in global memory).
-template <bool HAS_GAIN, bool HAS_MASK = false, bool MERGE = true>
+// sink (optional, as real_split_hook_merge's): called as sink(k, xk, xpk) in the loop's order.
+template <bool HAS_GAIN, bool HAS_MASK = false, bool MERGE = true, typename SINK = NoBinSink>
 __device__ __forceinline__ void split_merge(const cf* src, cf* dst, int p, const cf* st,
                                             const float* gain, cf* spec, int lane,
-                                            const float* mask = nullptr) {
+                                            const float* mask = nullptr, SINK sink = SINK()) {
     for (int k = lane; k < p; k += 64) {
         const cf zk = src[k];
         const cf fpnk = conj(src[(p - k) % p]);
@@ -249,6 +250,7 @@ __device__ __forceinline__ void split_merge(const cf* src, cf* dst, int p, const
             spec[k] = xk;
             if (k == 0) spec[p] = xpk;
         }
+        if constexpr (!std::is_same_v<SINK, NoBinSink>) sink(k, xk, xpk);
         if constexpr (MERGE) {
             const cf fek = {xk.r + xpk.r, xk.i - xpk.i};
             const cf tmp = {xk.r - xpk.r, xk.i + xpk.i};

@@ -20,6 +20,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 namespace crlot {
 namespace dev {
 
@@ -460,11 +462,17 @@ __device__ __forceinline__ cf dc_merge(cf x0, cf xp) { return {x0.r + xp.r, x0.r
 // mask[P-k] in the lane's registers -- multiplies re and im of X[k] and X[P-k]
 // (the step is (X * gain) * mask).  MERGE = false stops after the split (v is
 // left as it came: a forward transform that only writes its spectrum).
-template <int E, bool HAS_GAIN, bool WRITE_SPEC, bool HAS_MASK = false, bool MERGE = true>
+// sink (optional): called as sink(m, xk, xpk) with the step's X[k], X[P-k] of
+// k = lane + 64 m, in m order, for a caller that keeps the spectrum in registers.
+struct NoBinSink {
+    __device__ __forceinline__ void operator()(int, const cf&, const cf&) const {}
+};
+template <int E, bool HAS_GAIN, bool WRITE_SPEC, bool HAS_MASK = false, bool MERGE = true, typename SINK = NoBinSink>
 __device__ __forceinline__ void real_split_hook_merge(cf (&v)[E], cf* buf, const cf* st,
                                                       const cf* sth, const float* gain,
                                                       int lane, cf* spec = nullptr,
-                                                      const float* mk = nullptr, const float* mpk = nullptr) {
+                                                      const float* mk = nullptr, const float* mpk = nullptr,
+                                                      SINK sink = SINK()) {
     constexpr int P = 64 * E;
 #pragma unroll
     for (int m = 0; m < E; ++m) buf[lane + 64 * m] = v[m];  // conflict free unswizzled
@@ -501,6 +509,7 @@ __device__ __forceinline__ void real_split_hook_merge(cf (&v)[E], cf* buf, const
             spec[k] = xk;
             if (k == 0) spec[P] = xpk;
         }
+        if constexpr (!std::is_same_v<SINK, NoBinSink>) sink(m, xk, xpk);
         if constexpr (MERGE) {
             // kiss_fftri merge: Z'[k] = (X[k] + conj X[P-k]) + (X[k] - conj X[P-k]) conj(st)
             const cf w = st[k];

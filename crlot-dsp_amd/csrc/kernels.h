@@ -502,6 +502,15 @@ hipError_t launch_pair_feat(const Geometry& g, const DevTables& t, const FeatDev
 hipError_t launch_feat_step(const FeatDev& f, const float* spec, int64_t ld_spec, int64_t ld_row, int n_streams,
                             int64_t F, int bins, hipStream_t s);
 
+// stream_feat.hip: launch_stream_stft_hop with the feature epilogue (k_stream_feat /
+// k_stream_any_feat; one launch, the stft cut's grid and block).  Channel c's n_out
+// floats go to f.out + c f.ld_out on a hop that completes a frame (k >= 0); spec
+// (nullable) also gets stft_hop's row.  f.ld_frame is not read.
+hipError_t launch_stream_features_hop(const Geometry& g, const DevTables& t, const float* twany, bool any,
+                                      const FeatDev& f, const float* in, int64_t in_ld, int64_t in_inc, float* spec,
+                                      int64_t ld_spec, float* hist, int channels, int64_t q, int64_t k,
+                                      hipStream_t stream);
+
 // dsp::FrameQueue frames on the device: [stream][F][N] from x [stream][ld_x]
 hipError_t launch_fq_frames(const float* x, int64_t T, int64_t ld_x, int n_streams, float* frames, int64_t F,
                             int64_t N, int64_t H, int64_t pad, int pad_mode, hipStream_t s);

@@ -8,6 +8,7 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "feat_common.h"
 #include "fft_any.h"
 #include "fft_wave.h"
 #include "fused_common.h"
@@ -168,7 +169,10 @@ struct HopSpec {
 // kHopWhole: hop -> block (K_stream_hop; with a mask row K_stream_masked).
 // kHopStft: hop -> spectrum of the frame it completes, before the gain; acc untouched.
 // kHopIstft: spectrum of frame a.q -> (X gain) mask -> block a.q; hist untouched.
-enum : int { kHopWhole = 0, kHopStft = 1, kHopIstft = 2 };
+// kHopFeat: kHopStft up to and including the split; the spectrum stays in registers
+//   and its features (FeatDev: feat_common.h's per-bin value, band stage and log) go
+//   to channel c's row fd.out + c fd.ld_out; g.spec non-null: kHopStft's row as well.
+enum : int { kHopWhole = 0, kHopStft = 1, kHopIstft = 2, kHopFeat = 3 };
 
 // One hop of the low-latency path (BASELINE config 4): per channel, the last
 // NB = N/H hops live in `hist` (slot q mod NB holds hop q) and the OLA
@@ -179,10 +183,10 @@ enum : int { kHopWhole = 0, kHopStft = 1, kHopIstft = 2 };
 // The lane that owns frame sample i owns it in every frame (H % 128 == 0), so a
 // lane only ever touches its own acc words: no cross-lane hazards.
 template <int E, int S, int MODE, bool HAS_GAIN, bool HAS_MASK>
-__device__ __forceinline__ void stream_hop_body(const StreamArgs& a, const HopSpec& g) {
+__device__ __forceinline__ void stream_hop_body(const StreamArgs& a, const HopSpec& g, const FeatDev& fd = FeatDev{}) {
     constexpr int P = 64 * E, N = 2 * P, H = 128 * S, NB = E / S;
-    constexpr bool IN = MODE != kHopIstft;   // consumes a hop (hist)
-    constexpr bool OUT = MODE != kHopStft;   // produces a block (acc)
+    constexpr bool IN = MODE != kHopIstft;                       // consumes a hop (hist)
+    constexpr bool OUT = MODE == kHopWhole || MODE == kHopIstft;  // produces a block (acc)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     cf* tw = reinterpret_cast<cf*>(smem);
     cf* st = tw + P;
@@ -259,6 +263,15 @@ __device__ __forceinline__ void stream_hop_body(const StreamArgs& a, const HopSp
                           : make_float2(1.f, 1.f);
         }
     }
+    // kHopFeat: a filterbank that fits (feat_bank_in_lds) is staged behind the exchange
+    // buffers by the whole workgroup, dead waves included, on a hop that completes a
+    // frame: its loads go out with the hop's and land in front of the same barrier.
+    // A larger one is read through L2 by the band stage.
+    const bool bank_lds = MODE == kHopFeat && frame && feat_bank_in_lds(fd);
+    char* bank = reinterpret_cast<char*>(bufs + kWaves * xbuf_elems<P>());
+    if constexpr (MODE == kHopFeat) {
+        if (bank_lds) dev::feat_bank_stage(fd, bank, kBlock);
+    }
     if constexpr (HAS_MASK) {
         // The mask values are used only inside `if (frame)` behind the barrier, and
         // the compiler sinks their loads there (a second, exposed memory wait) unless
@@ -287,6 +300,43 @@ __device__ __forceinline__ void stream_hop_body(const StreamArgs& a, const HopSp
                 // the split alone, X before the gain, straight to the caller's row
                 dev::real_split_hook_merge<E, false, true, false, false>(
                     v, buf, st, sth, nullptr, lane, reinterpret_cast<cf*>(g.spec + int64_t(c) * g.ld_spec));
+            } else if constexpr (MODE == kHopFeat) {
+                // the same split; each lane keeps the values of its bins k = lane + 64 m (X[P]'s
+                // in lane 0), and stores X itself only when the caller gave a row (wave-uniform)
+                cf* srow = g.spec ? reinterpret_cast<cf*>(g.spec + int64_t(c) * g.ld_spec) : nullptr;
+                float val[E], val_p = 0.0f;
+                dev::real_split_hook_merge<E, false, false, false, false>(
+                    v, buf, st, sth, nullptr, lane, nullptr, nullptr, nullptr,
+                    [&](int m, const cf& xk, const cf& xpk) __attribute__((always_inline)) {
+                        const int k = lane + 64 * m;
+                        if (srow) {
+                            srow[k] = xk;
+                            if (k == 0) srow[P] = xpk;
+                        }
+                        val[m] = dev::feat_bin(xk.r, xk.i, fd.kind);
+                        if (m == 0) val_p = dev::feat_bin(xpk.r, xpk.i, fd.kind);
+                    });
+                float* row = fd.out + int64_t(c) * fd.ld_out;
+                if (fd.n_bands == 0) {
+#pragma unroll
+                    for (int m = 0; m < E; ++m) row[lane + 64 * m] = dev::feat_post(val[m], fd.log, fd.floor);
+                    if (lane == 0) row[P] = dev::feat_post(val_p, fd.log, fd.floor);
+                } else {
+                    // the wave's exchange buffer is free after the split (its reads are fenced):
+                    // P + 1 of its 2 P floats hold the values for the wave-local band stage
+                    float* vals = reinterpret_cast<float*>(buf);
+#pragma unroll
+                    for (int m = 0; m < E; ++m) vals[lane + 64 * m] = val[m];
+                    if (lane == 0) vals[P] = val_p;
+                    dev::wave_lds_fence();
+                    float* const rows[1] = {row};
+                    if (bank_lds) {
+                        const FeatBand* lb = reinterpret_cast<const FeatBand*>(bank);
+                        dev::feat_bands<1>(fd, lb, reinterpret_cast<const float*>(lb + fd.n_bands), vals, 0, rows, lane);
+                    } else {
+                        dev::feat_bands<1>(fd, fd.bands, fd.w, vals, 0, rows, lane);
+                    }
+                }
             } else {
                 dev::real_split_hook_merge<E, HAS_GAIN, false, HAS_MASK>(v, buf, st, sth, a.t.gain, lane, nullptr, mk,
                                                                          mpk);
@@ -346,9 +396,9 @@ __device__ __forceinline__ void stream_hop_body(const StreamArgs& a, const HopSp
 // wave-uniform; kHopIstft: k is the frame to synthesise), the frame runs through
 // the same arithmetic as K_fused_any and block k (H samples) is emitted.
 template <int MODE, bool HAS_GAIN, bool HAS_MASK>
-__device__ __forceinline__ void stream_any_body(const StreamAnyArgs& f, const HopSpec& g) {
+__device__ __forceinline__ void stream_any_body(const StreamAnyArgs& f, const HopSpec& g, const FeatDev& fd = FeatDev{}) {
     const AnyArgs& a = f.a;
-    constexpr bool IN = MODE != kHopIstft, OUT = MODE != kHopStft;
+    constexpr bool IN = MODE != kHopIstft, OUT = MODE == kHopWhole || MODE == kHopIstft;
     const int p = a.pl.p, n = 2 * p, H = a.h;
     const int lane = threadIdx.x & 63;
     const AnyLds l = any_lds<true>(a, IN);
@@ -390,6 +440,31 @@ __device__ __forceinline__ void stream_any_body(const StreamAnyArgs& f, const Ho
         if constexpr (MODE == kHopStft) {  // the split alone, X before the gain, to the caller's row
             dev::any::split_merge<false, false, false>(z, zo, p, l.st, nullptr,
                                                        reinterpret_cast<cf*>(g.spec + int64_t(c) * g.ld_spec), lane);
+            return;
+        } else if constexpr (MODE == kHopFeat) {
+            // the same split (and the same row when the caller gave one); the values of the
+            // lane's bins go to the row (per bin) or to the scratch side of A / B, which
+            // the split leaves alone, for the wave-local band stage (the bank through L2)
+            float* row = fd.out + int64_t(c) * fd.ld_out;
+            float* vals = reinterpret_cast<float*>(zo);  // p + 1 of its 2 p floats
+            const bool per_bin = fd.n_bands == 0;
+            dev::any::split_merge<false, false, false>(
+                z, zo, p, l.st, nullptr, g.spec ? reinterpret_cast<cf*>(g.spec + int64_t(c) * g.ld_spec) : nullptr,
+                lane, nullptr, [&](int b, const cf& xk, const cf& xpk) __attribute__((always_inline)) {
+                    const float vk = dev::feat_bin(xk.r, xk.i, fd.kind);
+                    if (per_bin) row[b] = dev::feat_post(vk, fd.log, fd.floor);
+                    else vals[b] = vk;
+                    if (b == 0) {
+                        const float vp = dev::feat_bin(xpk.r, xpk.i, fd.kind);
+                        if (per_bin) row[p] = dev::feat_post(vp, fd.log, fd.floor);
+                        else vals[p] = vp;
+                    }
+                });
+            if (!per_bin) {
+                dev::wave_lds_fence();
+                float* const rows[1] = {row};
+                dev::feat_bands<1>(fd, fd.bands, fd.w, vals, 0, rows, lane);
+            }
             return;
         } else {
             dev::any::split_merge<HAS_GAIN, HAS_MASK>(z, zo, p, l.st, a.t.gain, nullptr, lane, mr);

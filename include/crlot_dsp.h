@@ -575,6 +575,35 @@ int crlot_stream_istft_hop(crlot_stream* st, const float* d_spec, int64_t ld_spe
 int crlot_stream_push_hop_masked(crlot_stream* st, const float* d_hop_in, const float* d_mask, int64_t ld_mask,
                                  float* d_hop_out, int32_t* emitted, void* stream);
 
+/* Per-hop spectrogram features: stft_hop's analysis half with the features of a
+ * crlot_features object (created on the stream's plan) computed where the
+ * spectrum row would be stored -- what a mask model, a VAD or a streaming
+ * recogniser is fed -- in the same single launch.  Consumes H samples per
+ * channel (layout as push_hop); when the hop completes DROP frame k, channel c's
+ * n_out floats go to d_feat[c*ld_feat + j], channel-major whatever the PCM
+ * layout, ld_feat >= n_out, and *emitted = 1; otherwise *emitted = 0 and d_feat
+ * and d_spec are untouched.  d_spec != NULL: the launch also writes the spectrum
+ * row exactly as crlot_stream_stft_hop does (same layout rules and checks), so
+ * istft_hop(spec, mask(features)) can follow with no second analysis; d_spec =
+ * NULL: no spectrum reaches HBM and ld_spec is ignored.  A split-mode call: it
+ * advances stft_hop's hop counter and mixes freely with stft_hop; on a whole-mode
+ * object it is CRLOT_ERUNTIME until crlot_stream_reset.  CRLOT_EINVAL: a null st,
+ * f, d_hop_in or d_feat; f created on another plan than st's; ld_feat < n_out; a
+ * non-NULL d_spec that fails stft_hop's checks.  The features object is read
+ * stream-ordered and must outlive every hop enqueued with it.  Graph capture is
+ * not supported, as on the rest of this path.
+ * Value contract: X is bit for bit the row crlot_stream_stft_hop writes for that
+ * hop -- the per-frame transform, before the plan gain, no sanitize after the
+ * forward; the plan's frame-pairing setting plays no part (the hop path has no
+ * pairs).  From X onward the contract is crlot_spectrogram's, line for line:
+ * p = fl(fl(re re) + fl(im im)) with no FMA; the correctly rounded sqrtf for
+ * MAGNITUDE; the span / 8-part / tree summation order for bands; logf / log10f /
+ * 10 log10f of fmaxf(v, floor) of exactly the LIN value.  Output bits do not
+ * depend on the channel count, the PCM layout, ld_feat, whether d_spec is given,
+ * or where the kernel reads the filterbank from. */
+int crlot_stream_features_hop(crlot_stream* st, const crlot_features* f, const float* d_hop_in, float* d_feat,
+                              int64_t ld_feat, float* d_spec, int64_t ld_spec, int32_t* emitted, void* stream);
+
 /* ---------------------------------------------------------------- resident streaming
  * The same per-hop contract as crlot_stream_* (DROP Framer fed H samples per
  * channel per hop, push_frame_AoS + produce(H); framer.cc:37-117,

@@ -292,7 +292,7 @@ class SpectralStream {
     ~SpectralStream() { crlot_stream_destroy(st_); }
     SpectralStream(const SpectralStream&) = delete;
     SpectralStream& operator=(const SpectralStream&) = delete;
-    // each returns the samples (push_hop*: 0 or H) or spectra (stft_hop: 0 or 1) written per channel
+    // each returns the samples (push_hop*: 0 or H) or rows (stft_hop, features_hop: 0 or 1) written per channel
     size_t push_hop(const float* d_hop_in, float* d_hop_out, void* stream = nullptr) {
         int32_t em = 0;
         check(crlot_stream_push_hop(st_, d_hop_in, d_hop_out, &em, stream), "crlot_stream_push_hop");
@@ -308,6 +308,15 @@ class SpectralStream {
     size_t stft_hop(const float* d_hop_in, float* d_spec, int64_t ld_spec, void* stream = nullptr) {
         int32_t em = 0;
         check(crlot_stream_stft_hop(st_, d_hop_in, d_spec, ld_spec, &em, stream), "crlot_stream_stft_hop");
+        return size_t(em);
+    }
+    // stft_hop with the features where the spectrum would be stored (0 or 1 rows of f.n_out() floats per
+    // channel at d_feat + c*ld_feat); d_spec non-null: stft_hop's row as well, from the same launch
+    size_t features_hop(const Features& f, const float* d_hop_in, float* d_feat, int64_t ld_feat,
+                        float* d_spec = nullptr, int64_t ld_spec = 0, void* stream = nullptr) {
+        int32_t em = 0;
+        check(crlot_stream_features_hop(st_, f.get(), d_hop_in, d_feat, ld_feat, d_spec, ld_spec, &em, stream),
+              "crlot_stream_features_hop");
         return size_t(em);
     }
     void istft_hop(const float* d_spec, int64_t ld_spec, const float* d_mask, int64_t ld_mask, float* d_hop_out,
