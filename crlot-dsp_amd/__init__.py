@@ -147,6 +147,10 @@ def lib():
         "crlot_plan_set_spectral_mask": ([vp, vp, i64, i64], C.c_int),
         "crlot_stft": ([vp, vp, vp, i32, i64, i64, i64, i64, vp], C.c_int),
         "crlot_istft_ola": ([vp, vp, vp, i32, i64, i64, i64, i64, vp], C.c_int),
+        "crlot_stretch_frame_count": ([i64, C.c_double], i64),
+        "crlot_stretch_output_length": ([vp, i64, C.c_double], i64),
+        "crlot_phase_vocoder": ([vp, vp, vp, i32, i64, C.c_double, i64, i64, i64, i64, vp], C.c_int),
+        "crlot_time_stretch": ([vp, vp, vp, i32, i64, C.c_double, i64, i64, vp], C.c_int),
         "crlot_features_create": ([vp, C.POINTER(FeaturesDesc), vp, C.POINTER(vp)], C.c_int),
         "crlot_features_destroy": ([vp], None),
         "crlot_features_info": ([vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)], C.c_int),
@@ -405,6 +409,42 @@ def check_mask_extent(extent, n_streams: int, n_frames: int, what: str = "call")
         raise ValueError(f"{what}: the spectral mask has {s_mask} streams, the call has {n_streams}")
 
 
+def stretch_frame_count(F: int, rate: float) -> int:
+    """Frames a phase-vocoder stretch of F frames at `rate` gives: the number of
+    t >= 0 with t * rate < F (crlot_stretch_frame_count; rate in [1/64, 64])."""
+    return _check(int(lib().crlot_stretch_frame_count(int(F), float(rate))), "crlot_stretch_frame_count")
+
+
+def _stretch_spec_layout(shape, strides, dtype: str, device_index, plan_device: int, bins: int, what: str = "spec",
+                         expect=None):
+    """Validate a spectra tensor of Plan.phase_vocoder from its plain description
+    (shape and strides in complex elements as tuples, dtype name, device index or
+    None for a host tensor): (S, F, bins) complex64 on the plan's device, rows
+    contiguous and at least `bins` elements (N+2 floats) apart; `expect`: the exact
+    shape an output must have.  Returns (ld_spec, ld_frame) in floats."""
+    shape, strides = tuple(int(v) for v in shape), tuple(int(v) for v in strides)
+    if len(shape) != 3 or len(strides) != 3 or shape[2] != bins:
+        raise ValueError(f"{what} must be (S, F, N/2+1) or (F, N/2+1) complex64")
+    if expect is not None and shape != tuple(expect):
+        raise ValueError(f"{what} must be {tuple(expect)}, not {shape}")
+    if dtype != "complex64":
+        raise ValueError(f"{what} must be complex64, not {dtype}")
+    if device_index is None or int(device_index) != int(plan_device):
+        raise ValueError(f"{what} must live on the plan's device {plan_device}, not "
+                         f"{'the host' if device_index is None else device_index}")
+    if strides[2] != 1:
+        raise ValueError(f"{what} must have contiguous rows")
+    S, F = shape[0], shape[1]
+    # a size-1 dim's stride is meaningless: the dense value there
+    ld_frame = strides[1] if F > 1 else bins
+    ld_spec = strides[0] if S > 1 else max(F, 1) * ld_frame
+    if ld_frame < bins:
+        raise ValueError(f"{what} rows overlap: ld_frame < N+2 floats")
+    if S > 1 and ld_spec < (F - 1) * ld_frame + bins:
+        raise ValueError(f"{what} streams overlap: ld_spec too small")
+    return 2 * ld_spec, 2 * ld_frame
+
+
 def _stream_handle(tensor) -> int:
     torch = _torch()
     return int(torch.cuda.current_stream(tensor.device).cuda_stream)
@@ -588,6 +628,48 @@ class Plan:
         s = _stream_handle(spec) if stream is None else stream
         _check(lib().crlot_istft_ola(self._h, spec.data_ptr(), y.data_ptr(), S, F, 2 * _ld(spec, 0, F * bins),
                                      2 * _ld(spec, 1, bins), _ld(y, 0, L), s), "crlot_istft_ola")
+        return y
+
+    def stretch_output_length(self, T: int, rate: float) -> int:
+        return _check(int(lib().crlot_stretch_output_length(self._h, int(T), float(rate))),
+                      "crlot_stretch_output_length")
+
+    def phase_vocoder(self, spec, rate: float, out=None, stream: int | None = None):
+        """spec: (S, F, N/2+1) or (F, N/2+1) complex64 device tensor -> (S, F', N/2+1):
+        the spectra stretched in time by 1 / rate, F' = stretch_frame_count(F, rate)
+        (crlot_phase_vocoder; librosa / torchaudio phase_vocoder's recurrence)."""
+        if len(spec.shape) == 2:
+            return self.phase_vocoder(spec[None], rate, None if out is None else out[None], stream)[0]
+        bins = self.frame_size // 2 + 1
+        ld_in, ldf_in = _stretch_spec_layout(*_tensor_layout(spec), self._device_index(), bins)
+        S, F = int(spec.shape[0]), int(spec.shape[1])
+        Fp = stretch_frame_count(F, rate)
+        if out is None:
+            out = _torch().empty((S, Fp, bins), dtype=spec.dtype, device=spec.device)
+        ld_out, ldf_out = _stretch_spec_layout(*_tensor_layout(out), self._device_index(), bins, "out", (S, Fp, bins))
+        s = _stream_handle(spec) if stream is None else stream
+        _check(lib().crlot_phase_vocoder(self._h, spec.data_ptr(), out.data_ptr(), S, F, float(rate), ld_in, ldf_in,
+                                         ld_out, ldf_out, s), "crlot_phase_vocoder")
+        return out
+
+    def time_stretch(self, x, rate: float, y=None, stream: int | None = None):
+        """x: (S, T) or (T,) float32 device tensor -> y: (S, F' * H), the signal
+        stretched by 1 / rate at its pitch: istft_ola(phase_vocoder(stft(x), rate)),
+        bit for bit, with the spectra in the plan's scratch (crlot_time_stretch)."""
+        if x.dim() == 1:
+            return self.time_stretch(x[None], rate, None if y is None else y[None], stream)[0]
+        S, T = _spectrogram_x_layout(*_tensor_layout(x))
+        Fp = stretch_frame_count(self.frame_count(T), rate)
+        self._require_mask_covers(S, Fp, "time_stretch")
+        L = Fp * self.hop_size
+        if y is None:
+            y = _torch().empty((S, L), dtype=x.dtype, device=x.device)
+        if str(y.dtype) != "torch.float32" or not y.is_cuda or y.dim() != 2 or y.shape[0] != S or y.shape[1] < L or \
+                (y.shape[1] > 1 and y.stride(1) != 1):
+            raise ValueError(f"y must be a float32 device tensor of ({S}, >= {L}) with contiguous rows")
+        s = _stream_handle(x) if stream is None else stream
+        _check(lib().crlot_time_stretch(self._h, x.data_ptr(), y.data_ptr(), S, T, float(rate), _ld(x, 0, T),
+                                        _ld(y, 0, L), s), "crlot_time_stretch")
         return y
 
     # -- hot path

@@ -1192,21 +1192,23 @@ int stft_impl(crlot_plan* p, const float* d_x, float* d_spec, int32_t n_streams,
 // spectra as flat rows of N+2 floats (may be d_spec itself when that already
 // has this layout: the step runs in place), `frames` S F N floats.
 int istft_impl(crlot_plan* p, const float* d_spec, float* d_y, int32_t n_streams, int64_t F, int64_t ld_spec,
-               int64_t ld_frame, int64_t ld_y, float* specw, float* frames, hipStream_t s) {
+               int64_t ld_frame, int64_t ld_y, float* specw, float* frames, hipStream_t s,
+               const crlot::SpecMask* mask_at = nullptr) {
     const crlot::DevTables t = tables(p);
+    const crlot::SpecMask& mask = mask_at ? *mask_at : p->mask;  // (a slice of a batch: the stored mask at its first stream)
     hipError_t e;
     switch (istft_route(p, t, d_y, F, ld_y, n_streams).kind) {
         case RouteKind::kPair:  // (pairing off: K_istft, bit-identical to irfft + gather)
-            e = crlot::launch_pair_istft(p->geo, t, p->mask, d_spec, ld_spec, ld_frame, d_y, n_streams, F, ld_y, s);
+            e = crlot::launch_pair_istft(p->geo, t, mask, d_spec, ld_spec, ld_frame, d_y, n_streams, F, ld_y, s);
             return e == hipSuccess ? CRLOT_OK : hip_fail(e, "istft (frame pairs) kernel launch");
         case RouteKind::kPair15:  // (pairing off: the staged irfft + gather below)
-            e = crlot::launch_pair15_istft(p->geo, t, p->mask, d_spec, ld_spec, ld_frame, d_y, n_streams, F, ld_y, s);
+            e = crlot::launch_pair15_istft(p->geo, t, mask, d_spec, ld_spec, ld_frame, d_y, n_streams, F, ld_y, s);
             return e == hipSuccess ? CRLOT_OK : hip_fail(e, "istft (frame pairs, N = 960 / 480) kernel launch");
         case RouteKind::kPairN:  // (pairing off: the staged irfft + gather below)
-            e = crlot::launch_pairn_istft(p->geo, t, p->mask, d_spec, ld_spec, ld_frame, d_y, n_streams, F, ld_y, s);
+            e = crlot::launch_pairn_istft(p->geo, t, mask, d_spec, ld_spec, ld_frame, d_y, n_streams, F, ld_y, s);
             return e == hipSuccess ? CRLOT_OK : hip_fail(e, "istft (frame pairs, K_pairN sizes) kernel launch");
         case RouteKind::kWalk:
-            e = crlot::launch_istft(p->geo, t, p->mask, d_spec, ld_spec, ld_frame, d_y, n_streams, F, ld_y, s);
+            e = crlot::launch_istft(p->geo, t, mask, d_spec, ld_spec, ld_frame, d_y, n_streams, F, ld_y, s);
             return e == hipSuccess ? CRLOT_OK : hip_fail(e, "istft kernel launch");
         default: break;  // staged
     }
@@ -1215,8 +1217,8 @@ int istft_impl(crlot_plan* p, const float* d_spec, float* d_y, int32_t n_streams
     if (rows > INT32_MAX) return fail(CRLOT_EUNSUPPORTED, "too many frames for one call");
     const float* src = d_spec;
     int64_t ldf = ld_frame;
-    if (t.gain || p->mask.p || ld_spec != F * ld_frame) {
-        e = crlot::launch_spec_step(t, p->mask, d_spec, ld_spec, ld_frame, specw, n_streams, F, bins, s);
+    if (t.gain || mask.p || ld_spec != F * ld_frame) {
+        e = crlot::launch_spec_step(t, mask, d_spec, ld_spec, ld_frame, specw, n_streams, F, bins, s);
         if (e != hipSuccess) return hip_fail(e, "spectral step kernel launch");
         src = specw;
         ldf = 2 * bins;
@@ -1491,6 +1493,168 @@ int crlot_spectrogram(crlot_features* f, const float* d_x, float* d_out, int32_t
         fd.out = d_out + s0 * ld_out;
         const hipError_t e = crlot::launch_feat_step(fd, spec, F * row, row, ns, F, p->geo.n / 2 + 1, s);
         if (e != hipSuccess) return hip_fail(e, "feature step kernel launch");
+    }
+    return CRLOT_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------ time stretch
+// The phase vocoder between the two spectral entries (phase_voc.hip; the contract
+// is in include/crlot_dsp.h).  crlot_time_stretch runs crlot_stft's dispatch, the
+// vocoder and crlot_istft_ola's dispatch over slices of the streams, the spectra
+// in the stream's scratch slot.
+namespace {
+
+bool stretch_rate_ok(double rate) { return std::isfinite(rate) && rate >= 1.0 / 64 && rate <= 64.0; }
+
+// the number of t >= 0 with (double)t * rate < F (F >= 0, a valid rate): t * rate
+// is monotone in t, so the estimate is walked to the predicate's edge
+int64_t stretch_frames(int64_t F, double rate) {
+    if (F <= 0) return 0;
+    const double f = double(F);
+    int64_t n = int64_t(std::ceil(f / rate));
+    while (n > 0 && double(n - 1) * rate >= f) --n;
+    while (double(n) * rate < f) ++n;
+    return n;
+}
+constexpr int64_t kStretchMaxF = int64_t(1) << 52;  // (frame counts are exact doubles)
+
+// the vocoder's launches; `sums`: n_streams n_chunks bins int32 when n_chunks > 1
+int phase_voc_run(const crlot::PhaseVocArgs& a, int n_chunks, int m, int32_t* sums, hipStream_t s) {
+    const hipError_t e = crlot::launch_phase_voc(a, n_chunks, m, sums, s);
+    return e == hipSuccess ? CRLOT_OK : hip_fail(e, "phase vocoder kernel launch");
+}
+int64_t phase_voc_sums_bytes(int32_t n_streams, int n_chunks, int bins) {
+    return n_chunks > 1 ? int64_t(n_streams) * n_chunks * bins * int64_t(sizeof(int32_t)) : 0;
+}
+
+// do a_len floats at a and b_len floats at b intersect
+bool spec_ranges_overlap(const float* a, int64_t a_len, const float* b, int64_t b_len) {
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    return a0 < b0 + uintptr_t(b_len) * sizeof(float) && b0 < a0 + uintptr_t(a_len) * sizeof(float);
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t crlot_stretch_frame_count(int64_t F, double rate) {
+    if (F < 0 || F > kStretchMaxF) return fail(CRLOT_EINVAL, "bad frame count");
+    if (!stretch_rate_ok(rate)) return fail(CRLOT_EINVAL, "rate must be finite and in [1/64, 64]");
+    const int64_t n = stretch_frames(F, rate);
+    if (n > INT32_MAX) return fail(CRLOT_EINVAL, "too many stretched frames");
+    return n;
+}
+
+int64_t crlot_stretch_output_length(const crlot_plan* p, int64_t T, double rate) {
+    if (!p || T < 0) return fail(CRLOT_EINVAL, "bad argument");
+    const int64_t n = crlot_stretch_frame_count(frames_for(p, T), rate);
+    return n < 0 ? n : n * p->geo.h;
+}
+
+int crlot_phase_vocoder(crlot_plan* p, const float* d_in, float* d_out, int32_t n_streams, int64_t F, double rate,
+                        int64_t ld_spec_in, int64_t ld_frame_in, int64_t ld_spec_out, int64_t ld_frame_out,
+                        void* stream) {
+    if (!p) return fail(CRLOT_EINVAL, "null plan");
+    if (n_streams < 0 || F < 0) return fail(CRLOT_EINVAL, "negative size");
+    if (!stretch_rate_ok(rate)) return fail(CRLOT_EINVAL, "rate must be finite and in [1/64, 64]");
+    LaunchScope ls(p, stream);
+    if (n_streams == 0 || F == 0) return CRLOT_OK;
+    if (F > INT32_MAX) return fail(CRLOT_EUNSUPPORTED, "too many frames per stream");
+    const int64_t Fp = crlot_stretch_frame_count(F, rate);
+    if (Fp < 0) return int(Fp);
+    if (!d_in || !d_out) return fail(CRLOT_EINVAL, "null buffer");
+    const int64_t row = p->geo.n + 2;
+    if (ld_frame_in < row || ld_frame_out < row ||
+        (n_streams > 1 && (ld_spec_in < (F - 1) * ld_frame_in + row || ld_spec_out < (Fp - 1) * ld_frame_out + row)))
+        return fail(CRLOT_EINVAL, "leading dimension too small");
+    if (!aligned8(d_in) || !aligned8(d_out) || (ld_frame_in & 1) || (ld_frame_out & 1) ||
+        (n_streams > 1 && ((ld_spec_in & 1) || (ld_spec_out & 1))))
+        return fail(CRLOT_EINVAL, "spectra are complex float pairs: 8-byte aligned rows");
+    const int64_t in_len = (n_streams - 1) * ld_spec_in + (F - 1) * ld_frame_in + row;
+    const int64_t out_len = (n_streams - 1) * ld_spec_out + (Fp - 1) * ld_frame_out + row;
+    if (spec_ranges_overlap(d_in, in_len, d_out, out_len))
+        return fail(CRLOT_EINVAL, "the input and output spectra overlap");
+    DeviceGuard g(p->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    std::lock_guard<std::mutex> lk(p->mu);
+    const int bins = p->geo.n / 2 + 1;
+    int n_chunks = 1, m = 0;
+    crlot::phase_voc_chunks(n_streams, bins, Fp, n_chunks, m);
+    int32_t* sums = nullptr;
+    if (n_chunks > 1) {
+        crlot::Scratch* sc = scratch_slot(p, s);
+        if (!sc) return fail(CRLOT_EHIP, "scratch slot");
+        const int rc = ensure_workspace(sc, phase_voc_sums_bytes(n_streams, n_chunks, bins));
+        if (rc != CRLOT_OK) return rc;
+        sums = reinterpret_cast<int32_t*>(sc->work);
+    }
+    const crlot::PhaseVocArgs a{d_in, d_out, ld_spec_in, ld_frame_in, ld_spec_out, ld_frame_out, F, Fp, rate,
+                                n_streams, bins};
+    return phase_voc_run(a, n_chunks, m, sums, s);
+}
+
+int crlot_time_stretch(crlot_plan* p, const float* d_x, float* d_y, int32_t n_streams, int64_t T, double rate,
+                       int64_t ld_x, int64_t ld_y, void* stream) {
+    if (!p) return fail(CRLOT_EINVAL, "null plan");
+    if (n_streams < 0 || T < 0) return fail(CRLOT_EINVAL, "negative size");
+    if (!stretch_rate_ok(rate)) return fail(CRLOT_EINVAL, "rate must be finite and in [1/64, 64]");
+    LaunchScope ls(p, stream);
+    const int64_t F = frames_for(p, T);
+    if (n_streams == 0 || F == 0) return CRLOT_OK;
+    if (F > INT32_MAX) return fail(CRLOT_EUNSUPPORTED, "too many frames per stream");
+    const int64_t Fp = crlot_stretch_frame_count(F, rate);
+    if (Fp < 0) return int(Fp);
+    if (!d_x || !d_y) return fail(CRLOT_EINVAL, "null buffer");
+    if (ld_x < T || (n_streams > 1 && ld_y < Fp * p->geo.h)) return fail(CRLOT_EINVAL, "leading dimension too small");
+    DeviceGuard g(p->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    std::lock_guard<std::mutex> lk(p->mu);
+    crlot::Scratch* sc = scratch_slot(p, s);
+    if (!sc) return fail(CRLOT_EHIP, "scratch slot");
+    // Per stream: both spectra (flat rows of N+2 floats) and what the staged routes of
+    // the two halves add (the forward's windowed frames; the inverse's stepped spectra
+    // and frames), one after the other in the same floats.  A route does not depend on
+    // the slice: it follows the plan, the extents and the rows' alignment, which every
+    // slice shares.
+    const crlot::DevTables t = tables(p);
+    const int64_t n = p->geo.n, row = n + 2;
+    const int bins = p->geo.n / 2 + 1;
+    const bool in_staged = stft_route(p, t, d_x, T, ld_x, n_streams, F).kind == RouteKind::kStaged;
+    const bool out_staged = istft_route(p, t, d_y, Fp, ld_y, n_streams).kind == RouteKind::kStaged;
+    const int64_t stage = std::max<int64_t>(in_staged ? F * n : 0, out_staged ? Fp * (row + n) : 0);
+    const int64_t per_stream = (F * row + Fp * row + stage) * int64_t(sizeof(float));
+    const int64_t slice = std::max<int64_t>(1, std::min<int64_t>(n_streams, kFeatWorkspaceCap / per_stream));
+    // the vocoder's chunk sums behind them (chunked walks are those of small slices)
+    const int64_t tail = n_streams % slice;
+    int64_t sums_bytes = 0;
+    for (const int64_t ns : {slice, tail}) {
+        int nc = 1, m = 0;
+        if (ns > 0) crlot::phase_voc_chunks(int(ns), bins, Fp, nc, m);
+        sums_bytes = std::max(sums_bytes, phase_voc_sums_bytes(int32_t(ns), nc, bins));
+    }
+    int rc = ensure_workspace(sc, slice * per_stream + sums_bytes);
+    if (rc != CRLOT_OK) return rc;
+    float* spec_in = sc->work;
+    float* spec_out = spec_in + slice * F * row;
+    float* work = spec_out + slice * Fp * row;
+    int32_t* sums = reinterpret_cast<int32_t*>(work + slice * stage);
+    for (int64_t s0 = 0; s0 < n_streams; s0 += slice) {
+        const int32_t ns = int32_t(std::min<int64_t>(slice, n_streams - s0));
+        ls.ctl.rec = crlot::LaunchRecord{};  // (the record lists the last slice's launches)
+        rc = stft_impl(p, d_x + s0 * ld_x, spec_in, ns, T, ld_x, F, F * row, row, in_staged ? work : nullptr, s);
+        if (rc != CRLOT_OK) return rc;
+        int n_chunks = 1, m = 0;
+        crlot::phase_voc_chunks(ns, bins, Fp, n_chunks, m);
+        const crlot::PhaseVocArgs a{spec_in, spec_out, F * row, row, Fp * row, row, F, Fp, rate, ns, bins};
+        rc = phase_voc_run(a, n_chunks, m, sums, s);
+        if (rc != CRLOT_OK) return rc;
+        crlot::SpecMask mask = p->mask;
+        if (mask.p) mask.p += s0 * mask.ld_stream;
+        rc = istft_impl(p, spec_out, d_y + s0 * ld_y, ns, Fp, Fp * row, row, ld_y, out_staged ? work : nullptr,
+                        out_staged ? work + int64_t(ns) * Fp * row : nullptr, s, &mask);
+        if (rc != CRLOT_OK) return rc;
     }
     return CRLOT_OK;
 }

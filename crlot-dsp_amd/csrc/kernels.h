@@ -511,6 +511,24 @@ hipError_t launch_stream_features_hop(const Geometry& g, const DevTables& t, con
                                       int64_t ld_spec, float* hist, int channels, int64_t q, int64_t k,
                                       hipStream_t stream);
 
+// ---- phase_voc.hip: the phase vocoder (crlot_phase_vocoder; the contract is in include/crlot_dsp.h)
+// Spectra rows of `bins` float pairs, frame k of stream s at p + s ld_spec + k ld_frame
+// on either side; F rows in, Fp = crlot_stretch_frame_count(F, rate) rows out.
+struct PhaseVocArgs {
+    const float* in;
+    float* out;
+    int64_t ld_spec_in, ld_frame_in, ld_spec_out, ld_frame_out;
+    int64_t F, Fp;
+    double rate;
+    int32_t n_streams, bins;
+};
+// The split of [0, Fp) into n_chunks chunks of m output rows: one unless the
+// grid of n_streams ceil(bins / 64) waves under-fills the device (launch.cpp's
+// two-rounds chooser; the plan's chunk knob forces min(knob, Fp)).  Recorded.
+void phase_voc_chunks(int n_streams, int bins, int64_t Fp, int& n_chunks, int& m);
+// k_phase_voc, after k_phase_voc_sums when n_chunks > 1 (sums: n_streams n_chunks bins int32)
+hipError_t launch_phase_voc(const PhaseVocArgs& a, int n_chunks, int m, int32_t* sums, hipStream_t s);
+
 // dsp::FrameQueue frames on the device: [stream][F][N] from x [stream][ld_x]
 hipError_t launch_fq_frames(const float* x, int64_t T, int64_t ld_x, int n_streams, float* frames, int64_t F,
                             int64_t N, int64_t H, int64_t pad, int pad_mode, hipStream_t s);

@@ -175,6 +175,8 @@ extern "C" const char* crlot_kernel_name(int32_t id) {
         case CRLOT_K_FEAT: return "k_feat";
         case CRLOT_K_PAIR_FEAT: return "k_pair_feat";
         case CRLOT_K_FEAT_STEP: return "k_feat_step";
+        case CRLOT_K_PHASE_VOC: return "k_phase_voc";
+        case CRLOT_K_PHASE_VOC_SUMS: return "k_phase_voc_sums";
         case CRLOT_K_EXPERIMENT: return "k_experiment";
         default: return "unknown";
     }

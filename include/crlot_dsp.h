@@ -231,6 +231,8 @@ int crlot_test_inject(int32_t what, int32_t count);
 #define CRLOT_K_FEAT 32          /* crlot_spectrogram: one frame per wave (N = 256 / 512 / 1024) */
 #define CRLOT_K_PAIR_FEAT 33     /* crlot_spectrogram as frame pairs (N = 1024) */
 #define CRLOT_K_FEAT_STEP 34     /* crlot_spectrogram, staged: features of spectra in HBM */
+#define CRLOT_K_PHASE_VOC 35     /* crlot_phase_vocoder: spectra -> time-stretched spectra */
+#define CRLOT_K_PHASE_VOC_SUMS 36 /* ... the per-chunk phase increment sums, ahead of it when the walk is chunked */
 #define CRLOT_K_EXPERIMENT 99    /* experiment builds only */
 typedef struct crlot_launch_info {
     int32_t n_kernels;
@@ -433,6 +435,84 @@ int crlot_features_info(const crlot_features* f, int32_t* n_out, int32_t* kind, 
  * n_streams == 0: CRLOT_OK, nothing written. */
 int crlot_spectrogram(crlot_features* f, const float* d_x, float* d_out, int32_t n_streams, int64_t T,
                       int64_t ld_x, int64_t ld_out, int64_t ld_frame, void* stream);
+
+/* ---------------------------------------------------------------- time stretch
+ * The phase vocoder (librosa.phase_vocoder, torchaudio.functional.phase_vocoder)
+ * between crlot_stft and crlot_istft_ola: F frames in, F' frames out, duration
+ * changed by 1/rate, pitch kept.  rate is a finite double in [1/64, 64];
+ * rate > 1 shortens the signal.  Anything else is CRLOT_EINVAL.
+ *
+ * The time axis.
+ *   tau_t = (double)t * rate                     one IEEE double multiply
+ *   F' = crlot_stretch_frame_count(F, rate)      the number of t >= 0 with tau_t < F (this
+ *                                                predicate, not ceil(F / rate): the two differ by
+ *                                                one at some rates); F = 0 -> 0; F < 0, a bad
+ *                                                rate or F' > 2^31-1 -> CRLOT_EINVAL
+ *   i_t = floor(tau_t),  alpha_t = (float)(tau_t - i_t)
+ *   A frame with index >= F is all zeros and is never loaded from memory.
+ *   crlot_stretch_output_length(plan, T, rate) = F'(crlot_frame_count(T)) * H.
+ *
+ * The values, per stream and bin, X[k] being frame k of the input with both
+ * components sanitized on load as IFftPlan's sanitize does (NaN / Inf -> 0,
+ * |v| < 1e-30 -> 0):
+ *   q(z)  the phase of z in units of 2^-32 turn, a 32-bit integer modulo 2^32:
+ *           rint(fl(atan2f(im, re) * fl(2^32 / 2 pi))), 2^31 wrapping to -2^31; q(0) = 0
+ *           (fl(pi) * fl(1 / 2 pi) is exactly 1/2 in float32, so a negative real is exactly 2^31)
+ *   m(z)  sqrtf(fl(fl(re*re) + fl(im*im))), the CRLOT_FEAT_MAGNITUDE value (no FMA)
+ *   acc_0     = q(X[0])
+ *   acc_{t+1} = acc_t + q(X[i_t + 1]) - q(X[i_t])            wrapping 32-bit integer arithmetic
+ *   mag_t     = fl(fl(alpha_t * m(X[i_t + 1])) + fl(fl(1 - alpha_t) * m(X[i_t])))
+ *   out_t     = (mag_t * cos phi, mag_t * sin phi),  phi = 2 pi acc_t / 2^32
+ *               (the nearest quarter turn comes off acc_t in integers, exactly; the rest
+ *               goes through float32 radians: cos and sin are good to about 1.2e-7)
+ *   Bins 0 and N/2: input imaginary parts are ignored (taken as 0), output
+ *   imaginary parts are stored as +0.
+ * This is the librosa / torchaudio recurrence: their expected phase advance and
+ * the wrap to [-pi, pi] cancel modulo 2 pi, so the result does not depend on the hop.
+ * The integer accumulator has two consequences:
+ *   - the sum is associative and wraps a turn for free, so the output bits do not
+ *     depend on how the time axis is split into chunks (crlot_plan_set_chunks),
+ *     nor on n_streams, a stream's position in the batch or the leading dimensions;
+ *   - the phase error does not grow with the size of the accumulated phase, as it
+ *     does in a float32 cumulative sum; it grows with the number of steps alone
+ *     (each q is good to a few 2^-24 turn).
+ * Domain: magnitudes are exact to float32 rounding for components in
+ * {0} or [2^-60, 2^60] in size; beyond that re*re + im*im may overflow and m
+ * becomes +Inf (and the outputs Inf / NaN), or underflow to 0.  The float ->
+ * integer conversion only ever sees finite values of at most 2^31 in size.
+ *
+ * crlot_phase_vocoder: spectra in crlot_stft's layout on both sides -- bin b of
+ * frame k of stream s at d[s*ld_spec + k*ld_frame + 2*b], ld_frame >= N+2 floats,
+ * both leading dimensions even, base 8-byte aligned -- with independent leading
+ * dimensions; F frames per stream in, F' out.  The buffers must not overlap
+ * (CRLOT_EINVAL when the ranges intersect).  F = 0 or n_streams = 0: CRLOT_OK,
+ * nothing written.  F > 2^31-1: CRLOT_EUNSUPPORTED, as crlot_stft.  One lane owns
+ * one (stream, bin) column and walks its output frames in order with 64-bit
+ * addressing (no 2^27 / 2^29 extent limits).  A batch too small to fill the
+ * device splits [0, F') into chunks: CRLOT_K_PHASE_VOC_SUMS writes each chunk's
+ * increment sum per column into the stream's scratch slot and CRLOT_K_PHASE_VOC
+ * starts each chunk from the wrapped sum of the chunks before it;
+ * crlot_plan_set_chunks(n) forces min(n, F') chunks, crlot_plan_last_launch
+ * reports the kernels and n_chunks.
+ *
+ * crlot_time_stretch is by definition
+ * crlot_istft_ola(crlot_phase_vocoder(crlot_stft(x))) on the plan, bit for bit:
+ * framing is the plan's; the plan's gain and stored mask apply to the stretched
+ * frames (a mask must hold F' rows; the Python binding checks this before the
+ * call); it writes d_y[s*ld_y + n] for n < F' * H.  The spectra live in the
+ * stream's scratch slot; the streams are processed in slices whose workspace
+ * (both spectra and the staged routes' frames) stays within 256 MiB, or one
+ * stream's worth if that is more.  crlot_plan_last_launch lists the last
+ * slice's kernels in launch order (the analysis half's, CRLOT_K_PHASE_VOC_SUMS
+ * when that slice's walk is chunked, CRLOT_K_PHASE_VOC, the synthesis half's);
+ * its n_chunks is that of the last chunked walk among them. */
+int64_t crlot_stretch_frame_count(int64_t F, double rate); /* host only, no device */
+int64_t crlot_stretch_output_length(const crlot_plan* plan, int64_t T, double rate);
+int crlot_phase_vocoder(crlot_plan* plan, const float* d_spec_in, float* d_spec_out, int32_t n_streams,
+                        int64_t F, double rate, int64_t ld_spec_in, int64_t ld_frame_in,
+                        int64_t ld_spec_out, int64_t ld_frame_out, void* stream);
+int crlot_time_stretch(crlot_plan* plan, const float* d_x, float* d_y, int32_t n_streams, int64_t T,
+                       double rate, int64_t ld_x, int64_t ld_y, void* stream);
 /* host helpers (no device) */
 #define CRLOT_MEL_HTK 0
 #define CRLOT_MEL_SLANEY 1

@@ -173,6 +173,25 @@ class StftEngine {
         check(crlot_istft_ola(plan_.get(), d_spec, d_y, n_streams, F, ld_spec, ld_frame, ld_y, s),
               "crlot_istft_ola");
     }
+    // Time stretch by 1 / rate at the signal's pitch (the phase vocoder; rate in [1/64, 64]).
+    // F frames become stretch_frame_count(F, rate); T samples stretch_output_length(T, rate).
+    static int64_t stretch_frame_count(int64_t F, double rate) { return crlot_stretch_frame_count(F, rate); }
+    int64_t stretch_output_length(int64_t T, double rate) const {
+        return crlot_stretch_output_length(plan_.get(), T, rate);
+    }
+    // spectra (F frames per stream) -> stretched spectra, both in stft_device's layout; no overlap
+    void phase_vocoder_device(const float* d_spec_in, float* d_spec_out, int n_streams, int64_t F, double rate,
+                              int64_t ld_spec_in, int64_t ld_frame_in, int64_t ld_spec_out, int64_t ld_frame_out,
+                              hipStream_t s = nullptr) {
+        check(crlot_phase_vocoder(plan_.get(), d_spec_in, d_spec_out, n_streams, F, rate, ld_spec_in, ld_frame_in,
+                                  ld_spec_out, ld_frame_out, s),
+              "crlot_phase_vocoder");
+    }
+    // x -> istft_ola(phase_vocoder(stft(x))): d_y [n_streams][ld_y], stretch_output_length(T, rate) samples each
+    void time_stretch_device(const float* d_x, float* d_y, int n_streams, int64_t T, double rate, int64_t ld_x,
+                             int64_t ld_y, hipStream_t s = nullptr) {
+        check(crlot_time_stretch(plan_.get(), d_x, d_y, n_streams, T, rate, ld_x, ld_y, s), "crlot_time_stretch");
+    }
     // per-frame real mask rows of bins(): frame k of stream s at d_mask + s*ld_stream + k*ld_frame
     // (ld_stream 0: one mask shared by the streams); nullptr clears it
     void set_spectral_mask(const float* d_mask_or_null, int64_t ld_frame = 0, int64_t ld_stream = 0) {
