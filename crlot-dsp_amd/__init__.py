@@ -90,6 +90,25 @@ class FeaturesDesc(C.Structure):
     _fields_ = [("kind", C.c_int32), ("n_bands", C.c_int32), ("log", C.c_int32), ("floor", C.c_float)]
 
 
+class ResamplerDesc(C.Structure):
+    """crlot_resampler_desc (include/crlot_dsp.h)."""
+    _fields_ = [("up", C.c_int32), ("down", C.c_int32), ("zeros", C.c_int32), ("window", C.c_int32),
+                ("rolloff", C.c_double), ("beta", C.c_double), ("device", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ResamplerGeometry(C.Structure):
+    """crlot_resampler_geometry (include/crlot_dsp.h)."""
+    _fields_ = [("up", C.c_int32), ("down", C.c_int32), ("half_width", C.c_int32), ("taps", C.c_int32),
+                ("phase_ok", C.c_int32), ("device", C.c_int32)]
+
+
+class ResampleLaunch(C.Structure):
+    """crlot_resample_launch (include/crlot_dsp.h): a resampler's last launch."""
+    _fields_ = [("kernel", C.c_int32), ("threads", C.c_int32), ("grid", C.c_int64), ("tile_outputs", C.c_int64),
+                ("tile", C.c_int32), ("groups", C.c_int32), ("taps_padded", C.c_int32), ("lds_table", C.c_int32),
+                ("lds_bytes", C.c_int64)]
+
+
 class FftDesc(C.Structure):
     """crlot_fft_desc (include/crlot_dsp.h)."""
     _fields_ = [("domain", C.c_int32), ("nfft", C.c_int32), ("device", C.c_int32)]
@@ -151,6 +170,20 @@ def lib():
         "crlot_stretch_output_length": ([vp, i64, C.c_double], i64),
         "crlot_phase_vocoder": ([vp, vp, vp, i32, i64, C.c_double, i64, i64, i64, i64, vp], C.c_int),
         "crlot_time_stretch": ([vp, vp, vp, i32, i64, C.c_double, i64, i64, vp], C.c_int),
+        "crlot_resample_geometry": ([C.POINTER(ResamplerDesc), C.POINTER(ResamplerGeometry)], C.c_int),
+        "crlot_resample_table_host": ([C.POINTER(ResamplerDesc), fp], C.c_int),
+        "crlot_rational_approx": ([C.c_double, i32, C.POINTER(i32), C.POINTER(i32)], C.c_int),
+        "crlot_resampler_create": ([C.POINTER(ResamplerDesc), C.POINTER(vp)], C.c_int),
+        "crlot_resampler_destroy": ([vp], None),
+        "crlot_resampler_info": ([vp, C.POINTER(ResamplerGeometry)], C.c_int),
+        "crlot_resampler_table": ([vp, fp], C.c_int),
+        "crlot_resampler_prepare": ([vp], C.c_int),
+        "crlot_resample_output_length": ([vp, i64], i64),
+        "crlot_resampler_set_route": ([vp, i32], C.c_int),
+        "crlot_resampler_set_tile": ([vp, i32], C.c_int),
+        "crlot_resampler_last_launch": ([vp, C.POINTER(ResampleLaunch)], C.c_int),
+        "crlot_resample": ([vp, vp, vp, i32, i64, i64, i64, vp], C.c_int),
+        "crlot_pitch_shift": ([vp, vp, vp, vp, i32, i64, i64, i64, vp], C.c_int),
         "crlot_features_create": ([vp, C.POINTER(FeaturesDesc), vp, C.POINTER(vp)], C.c_int),
         "crlot_features_destroy": ([vp], None),
         "crlot_features_info": ([vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)], C.c_int),
@@ -672,6 +705,38 @@ class Plan:
                                         _ld(y, 0, L), s), "crlot_time_stretch")
         return y
 
+    def pitch_shift(self, x, resampler=None, semitones: float | None = None, max_den: int = 256, y=None,
+                    stream: int | None = None):
+        """x: (S, T) or (T,) float32 device tensor -> y: (S, T), the pitch multiplied
+        by D / U of `resampler` (a Resampler(U, D, ...) on the plan's device) at the
+        same length: resample(time_stretch(x, U / D)) cropped or zero-filled to T, bit
+        for bit (crlot_pitch_shift).  semitones instead of a resampler: the ratio
+        2 ** (semitones / 12) through rational_approx(., max_den) and a Resampler with
+        the default filter, cached on the plan."""
+        if (resampler is None) == (semitones is None):
+            raise ValueError("give either a resampler or semitones")
+        if resampler is None:
+            num, den = rational_approx(2.0 ** (float(semitones) / 12.0), max_den)
+            cache = self.__dict__.setdefault("_pitch_resamplers", {})
+            resampler = cache.get((den, num))
+            if resampler is None:  # (pitch * num / den: D = num, U = den)
+                resampler = cache[(den, num)] = Resampler(den, num, device=self._device_index())
+        if x.dim() == 1:
+            return self.pitch_shift(x[None], resampler, None, max_den, None if y is None else y[None], stream)[0]
+        S, T = _spectrogram_x_layout(*_tensor_layout(x))
+        if resampler.device != self._device_index():
+            raise ValueError(f"the resampler is on device {resampler.device}, the plan on {self._device_index()}")
+        rate = resampler.up / resampler.down
+        if T > 0 and self.frame_count(T) > 0:
+            self._require_mask_covers(S, stretch_frame_count(self.frame_count(T), rate), "pitch_shift")
+        if y is None:
+            y = _torch().empty((S, T), dtype=x.dtype, device=x.device)
+        ld_y = _resample_y_layout(*_tensor_layout(y), S, T)
+        s = _stream_handle(x) if stream is None else stream
+        _check(lib().crlot_pitch_shift(self._h, resampler._h, x.data_ptr(), y.data_ptr(), S, T, _ld(x, 0, T), ld_y, s),
+               "crlot_pitch_shift")
+        return y
+
     # -- hot path
     def roundtrip(self, x, y=None, stream: int | None = None):
         """x: (S, T) float32 CUDA tensor -> y: (S, F*H)."""
@@ -898,6 +963,138 @@ class Features:
         _check(lib().crlot_spectrogram(self._h, x.data_ptr(), out.data_ptr(), S, T, _ld(x, 0, T), ld_out, ld_frame,
                                        s), "crlot_spectrogram")
         return out
+
+
+# ----------------------------------------------------------------- resampler
+RESAMPLE_HANN, RESAMPLE_KAISER = 0, 1
+RESAMPLE_AUTO, RESAMPLE_PHASE, RESAMPLE_ANY = 0, 1, 2
+_RESAMPLE_WINDOWS = {"hann": RESAMPLE_HANN, "kaiser": RESAMPLE_KAISER}
+_RESAMPLE_ROUTES = {"auto": RESAMPLE_AUTO, "phase": RESAMPLE_PHASE, "any": RESAMPLE_ANY}
+
+
+def rational_approx(ratio: float, max_den: int) -> tuple[int, int]:
+    """The best rational (num, den) to `ratio` with den <= max_den: exactly
+    fractions.Fraction(ratio).limit_denominator(max_den) (crlot_rational_approx)."""
+    num, den = C.c_int32(), C.c_int32()
+    _check(lib().crlot_rational_approx(float(ratio), int(max_den), C.byref(num), C.byref(den)),
+           "crlot_rational_approx")
+    return num.value, den.value
+
+
+def _resampler_desc(up, down, zeros=16, rolloff=0.95, window="hann", beta=8.6, device=0) -> ResamplerDesc:
+    if isinstance(window, str):
+        if window not in _RESAMPLE_WINDOWS:
+            raise ValueError(f"window must be one of {sorted(_RESAMPLE_WINDOWS)}")
+        window = _RESAMPLE_WINDOWS[window]
+    return ResamplerDesc(int(up), int(down), int(zeros), int(window), float(rolloff), float(beta), int(device), 0)
+
+
+def resample_geometry(up, down, zeros=16, rolloff=0.95, window="hann", beta=8.6, device=0) -> dict:
+    """The reduced rates and filter geometry of a descriptor, on the host
+    (crlot_resample_geometry): up, down, half_width W, taps K, phase_ok."""
+    d, g = _resampler_desc(up, down, zeros, rolloff, window, beta, device), ResamplerGeometry()
+    _check(lib().crlot_resample_geometry(C.byref(d), C.byref(g)), "crlot_resample_geometry")
+    return {k: getattr(g, k) for k, _ in ResamplerGeometry._fields_}
+
+
+def resample_table_host(up, down, zeros=16, rolloff=0.95, window="hann", beta=8.6) -> np.ndarray:
+    """The (U, K) float32 filter table of a descriptor, built on the host
+    (crlot_resample_table_host)."""
+    g = resample_geometry(up, down, zeros, rolloff, window, beta)
+    d = _resampler_desc(up, down, zeros, rolloff, window, beta)
+    out = np.zeros((g["up"], g["taps"]), np.float32)
+    _check(lib().crlot_resample_table_host(C.byref(d), _fptr(out)), "crlot_resample_table_host")
+    return out
+
+
+def _resample_y_layout(shape, strides, dtype: str, device_index, S: int, L: int, what: str = "y"):
+    """Validate a resampler output from its plain description: (S, >= L) float32 on
+    the device with contiguous rows.  Returns ld_y."""
+    if dtype != "float32" or device_index is None:
+        raise ValueError(f"{what} must be a float32 device tensor")
+    if len(shape) != 2 or len(strides) != 2 or int(shape[0]) != S or int(shape[1]) < L:
+        raise ValueError(f"{what} must be ({S}, >= {L})")
+    if int(shape[1]) > 1 and int(strides[1]) != 1:
+        raise ValueError(f"{what} must have contiguous rows")
+    ld = int(strides[0]) if S > 1 else max(int(shape[1]), L)  # (a size-1 dim's stride is meaningless)
+    if S > 1 and ld < L:
+        raise ValueError(f"{what} rows overlap: ld_y < {L}")
+    return ld
+
+
+class Resampler:
+    """A band-limited rational resampler from rate `down` to rate `up`
+    (crlot_resampler_create / crlot_resample): the polyphase windowed-sinc filter of
+    torchaudio.functional.resample, `zeros` zero crossings wide, Hann or Kaiser
+    windowed.  Needs no plan; the table is uploaded by the first call."""
+
+    def __init__(self, up: int, down: int, zeros: int = 16, rolloff: float = 0.95, window="hann", beta: float = 8.6,
+                 device: int = 0):
+        self._h = None
+        d = _resampler_desc(up, down, zeros, rolloff, window, beta, device)
+        h = C.c_void_p()
+        _check(lib().crlot_resampler_create(C.byref(d), C.byref(h)), "crlot_resampler_create")
+        self._h = h
+        g = ResamplerGeometry()
+        _check(lib().crlot_resampler_info(self._h, C.byref(g)), "crlot_resampler_info")
+        self.info = {k: getattr(g, k) for k, _ in ResamplerGeometry._fields_}
+        self.up, self.down, self.half_width, self.taps, self.device = g.up, g.down, g.half_width, g.taps, g.device
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().crlot_resampler_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # interpreter shutdown
+            pass
+
+    def output_length(self, T: int) -> int:
+        return _check(int(lib().crlot_resample_output_length(self._h, int(T))), "crlot_resample_output_length")
+
+    def table(self) -> np.ndarray:
+        out = np.zeros((self.up, self.taps), np.float32)
+        _check(lib().crlot_resampler_table(self._h, _fptr(out)), "crlot_resampler_table")
+        return out
+
+    def prepare(self):
+        _check(lib().crlot_resampler_prepare(self._h), "crlot_resampler_prepare")
+
+    def set_route(self, route):
+        """"auto", "phase" or "any" (RESAMPLE_*): a test knob; "phase" on a shape the
+        phase kernel cannot take raises NotImplementedError."""
+        route = _RESAMPLE_ROUTES[route] if isinstance(route, str) else int(route)
+        _check(lib().crlot_resampler_set_route(self._h, route), "crlot_resampler_set_route")
+
+    def set_tile(self, n_blocks: int):
+        """Force n output blocks of U outputs per tile (0: the library's choice)."""
+        _check(lib().crlot_resampler_set_tile(self._h, int(n_blocks)), "crlot_resampler_set_tile")
+
+    def last_launch(self) -> dict:
+        r = ResampleLaunch()
+        _check(lib().crlot_resampler_last_launch(self._h, C.byref(r)), "crlot_resampler_last_launch")
+        d = {k: getattr(r, k) for k, _ in ResampleLaunch._fields_}
+        d["name"] = kernel_name(r.kernel) if r.kernel else None
+        return d
+
+    def resample(self, x, y=None, stream: int | None = None):
+        """x: (S, T) or (T,) float32 device tensor -> y: (S, L), L = output_length(T)
+        (crlot_resample)."""
+        if x.dim() == 1:
+            return self.resample(x[None], None if y is None else y[None], stream)[0]
+        S, T = _spectrogram_x_layout(*_tensor_layout(x))
+        if (x.device.index or 0) != self.device:
+            raise ValueError(f"x must live on the resampler's device {self.device}")
+        L = self.output_length(T)
+        if y is None:
+            y = _torch().empty((S, L), dtype=x.dtype, device=x.device)
+        ld_y = _resample_y_layout(*_tensor_layout(y), S, L)
+        s = _stream_handle(x) if stream is None else stream
+        _check(lib().crlot_resample(self._h, x.data_ptr(), y.data_ptr(), S, T, _ld(x, 0, T), ld_y, s),
+               "crlot_resample")
+        return y
 
 
 class FftPlan:

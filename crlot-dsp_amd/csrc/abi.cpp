@@ -1535,6 +1535,80 @@ bool spec_ranges_overlap(const float* a, int64_t a_len, const float* b, int64_t 
     return a0 < b0 + uintptr_t(b_len) * sizeof(float) && b0 < a0 + uintptr_t(a_len) * sizeof(float);
 }
 
+// What crlot_pitch_shift adds behind each slice's time stretch: the stretched
+// slice z stays in the workspace and the resampler writes T outputs per stream.
+struct PitchTail {
+    crlot_resampler* r;
+    float* d_y;
+    int64_t ld_y;
+};
+
+// crlot_time_stretch's body; the caller has checked the arguments and holds the
+// plan's lock.  With a tail, d_y / ld_y are unused: each slice's output goes to z,
+// dense rows of F' H floats behind the time stretch's workspace, and from there
+// through the resampler to tail->d_y.
+int time_stretch_locked(crlot_plan* p, LaunchScope& ls, const float* d_x, float* d_y, int32_t n_streams, int64_t T,
+                        int64_t F, int64_t Fp, double rate, int64_t ld_x, int64_t ld_y, hipStream_t s,
+                        const PitchTail* tail) {
+    crlot::Scratch* sc = scratch_slot(p, s);
+    if (!sc) return fail(CRLOT_EHIP, "scratch slot");
+    // Per stream: both spectra (flat rows of N+2 floats) and what the staged routes of
+    // the two halves add (the forward's windowed frames; the inverse's stepped spectra
+    // and frames), one after the other in the same floats.  A route does not depend on
+    // the slice: it follows the plan, the extents and the rows' alignment, which every
+    // slice shares.
+    const crlot::DevTables t = tables(p);
+    const int64_t n = p->geo.n, row = n + 2;
+    const int bins = p->geo.n / 2 + 1;
+    const bool in_staged = stft_route(p, t, d_x, T, ld_x, n_streams, F).kind == RouteKind::kStaged;
+    // (z: the workspace is 256-byte aligned and z starts a multiple of 64 floats into
+    // it; a route reads the pointer's alignment alone)
+    const int64_t Ls = Fp * p->geo.h;
+    if (tail) d_y = reinterpret_cast<float*>(uintptr_t(256)), ld_y = Ls;
+    const bool out_staged = istft_route(p, t, d_y, Fp, ld_y, n_streams).kind == RouteKind::kStaged;
+    const int64_t stage = std::max<int64_t>(in_staged ? F * n : 0, out_staged ? Fp * (row + n) : 0);
+    const int64_t per_stream = (F * row + Fp * row + stage + (tail ? Ls : 0)) * int64_t(sizeof(float));
+    const int64_t slice = std::max<int64_t>(1, std::min<int64_t>(n_streams, kFeatWorkspaceCap / per_stream));
+    // the vocoder's chunk sums behind them (chunked walks are those of small slices)
+    const int64_t last = n_streams % slice;
+    int64_t sums_bytes = 0;
+    for (const int64_t ns : {slice, last}) {
+        int nc = 1, m = 0;
+        if (ns > 0) crlot::phase_voc_chunks(int(ns), bins, Fp, nc, m);
+        sums_bytes = std::max(sums_bytes, phase_voc_sums_bytes(int32_t(ns), nc, bins));
+    }
+    const int64_t z_at = (slice * (F * row + Fp * row + stage) + sums_bytes / int64_t(sizeof(float)) + 63) / 64 * 64;
+    int rc = ensure_workspace(sc, tail ? (z_at + slice * Ls) * int64_t(sizeof(float)) : slice * per_stream + sums_bytes);
+    if (rc != CRLOT_OK) return rc;
+    if (tail) d_y = sc->work + z_at;
+    float* spec_in = sc->work;
+    float* spec_out = spec_in + slice * F * row;
+    float* work = spec_out + slice * Fp * row;
+    int32_t* sums = reinterpret_cast<int32_t*>(work + slice * stage);
+    for (int64_t s0 = 0; s0 < n_streams; s0 += slice) {
+        const int32_t ns = int32_t(std::min<int64_t>(slice, n_streams - s0));
+        ls.ctl.rec = crlot::LaunchRecord{};  // (the record lists the last slice's launches)
+        rc = stft_impl(p, d_x + s0 * ld_x, spec_in, ns, T, ld_x, F, F * row, row, in_staged ? work : nullptr, s);
+        if (rc != CRLOT_OK) return rc;
+        int n_chunks = 1, m = 0;
+        crlot::phase_voc_chunks(ns, bins, Fp, n_chunks, m);
+        const crlot::PhaseVocArgs a{spec_in, spec_out, F * row, row, Fp * row, row, F, Fp, rate, ns, bins};
+        rc = phase_voc_run(a, n_chunks, m, sums, s);
+        if (rc != CRLOT_OK) return rc;
+        crlot::SpecMask mask = p->mask;
+        if (mask.p) mask.p += s0 * mask.ld_stream;
+        float* y_slice = tail ? d_y : d_y + s0 * ld_y;
+        rc = istft_impl(p, spec_out, y_slice, ns, Fp, Fp * row, row, ld_y, out_staged ? work : nullptr,
+                        out_staged ? work + int64_t(ns) * Fp * row : nullptr, s, &mask);
+        if (rc != CRLOT_OK) return rc;
+        if (tail) {
+            rc = crlot::resample_run(tail->r, y_slice, tail->d_y + s0 * tail->ld_y, ns, Ls, T, ld_y, tail->ld_y, s);
+            if (rc != CRLOT_OK) return rc;
+        }
+    }
+    return CRLOT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1611,52 +1685,39 @@ int crlot_time_stretch(crlot_plan* p, const float* d_x, float* d_y, int32_t n_st
     DeviceGuard g(p->device);
     hipStream_t s = static_cast<hipStream_t>(stream);
     std::lock_guard<std::mutex> lk(p->mu);
-    crlot::Scratch* sc = scratch_slot(p, s);
-    if (!sc) return fail(CRLOT_EHIP, "scratch slot");
-    // Per stream: both spectra (flat rows of N+2 floats) and what the staged routes of
-    // the two halves add (the forward's windowed frames; the inverse's stepped spectra
-    // and frames), one after the other in the same floats.  A route does not depend on
-    // the slice: it follows the plan, the extents and the rows' alignment, which every
-    // slice shares.
-    const crlot::DevTables t = tables(p);
-    const int64_t n = p->geo.n, row = n + 2;
-    const int bins = p->geo.n / 2 + 1;
-    const bool in_staged = stft_route(p, t, d_x, T, ld_x, n_streams, F).kind == RouteKind::kStaged;
-    const bool out_staged = istft_route(p, t, d_y, Fp, ld_y, n_streams).kind == RouteKind::kStaged;
-    const int64_t stage = std::max<int64_t>(in_staged ? F * n : 0, out_staged ? Fp * (row + n) : 0);
-    const int64_t per_stream = (F * row + Fp * row + stage) * int64_t(sizeof(float));
-    const int64_t slice = std::max<int64_t>(1, std::min<int64_t>(n_streams, kFeatWorkspaceCap / per_stream));
-    // the vocoder's chunk sums behind them (chunked walks are those of small slices)
-    const int64_t tail = n_streams % slice;
-    int64_t sums_bytes = 0;
-    for (const int64_t ns : {slice, tail}) {
-        int nc = 1, m = 0;
-        if (ns > 0) crlot::phase_voc_chunks(int(ns), bins, Fp, nc, m);
-        sums_bytes = std::max(sums_bytes, phase_voc_sums_bytes(int32_t(ns), nc, bins));
+    return time_stretch_locked(p, ls, d_x, d_y, n_streams, T, F, Fp, rate, ld_x, ld_y, s, nullptr);
+}
+
+int crlot_pitch_shift(crlot_plan* p, crlot_resampler* r, const float* d_x, float* d_y, int32_t n_streams, int64_t T,
+                      int64_t ld_x, int64_t ld_y, void* stream) {
+    if (!p) return fail(CRLOT_EINVAL, "null plan");
+    if (!r) return fail(CRLOT_EINVAL, "null resampler");
+    if (n_streams < 0 || T < 0) return fail(CRLOT_EINVAL, "negative size");
+    int32_t U = 1, D = 1, dev = 0;
+    crlot::resampler_rates(r, U, D, dev);
+    const double rate = double(U) / double(D);
+    if (!stretch_rate_ok(rate)) return fail(CRLOT_EINVAL, "rate must be finite and in [1/64, 64]");
+    if (dev != p->device) return fail(CRLOT_EINVAL, "the plan and the resampler are on different devices");
+    LaunchScope ls(p, stream);
+    if (n_streams == 0 || T == 0) return CRLOT_OK;
+    const int64_t F = frames_for(p, T);
+    if (F > INT32_MAX) return fail(CRLOT_EUNSUPPORTED, "too many frames per stream");
+    const int64_t Fp = F > 0 ? crlot_stretch_frame_count(F, rate) : 0;
+    if (Fp < 0) return int(Fp);
+    if (!d_x || !d_y) return fail(CRLOT_EINVAL, "null buffer");
+    if (ld_x < T || (n_streams > 1 && ld_y < T)) return fail(CRLOT_EINVAL, "leading dimension too small");
+    if (spec_ranges_overlap(d_x, (n_streams - 1) * ld_x + T, d_y, (n_streams - 1) * ld_y + T))
+        return fail(CRLOT_EINVAL, "the input and output overlap");
+    DeviceGuard g(p->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    std::lock_guard<std::mutex> lk(p->mu);
+    if (Fp == 0) {  // (no frame: the stretch is empty and every output is fix_length's +0)
+        const size_t pitch = size_t(n_streams > 1 ? ld_y : T) * sizeof(float);
+        const hipError_t e = hipMemset2DAsync(d_y, pitch, 0, size_t(T) * sizeof(float), size_t(n_streams), s);
+        return e == hipSuccess ? CRLOT_OK : hip_fail(e, "pitch shift zero fill");
     }
-    int rc = ensure_workspace(sc, slice * per_stream + sums_bytes);
-    if (rc != CRLOT_OK) return rc;
-    float* spec_in = sc->work;
-    float* spec_out = spec_in + slice * F * row;
-    float* work = spec_out + slice * Fp * row;
-    int32_t* sums = reinterpret_cast<int32_t*>(work + slice * stage);
-    for (int64_t s0 = 0; s0 < n_streams; s0 += slice) {
-        const int32_t ns = int32_t(std::min<int64_t>(slice, n_streams - s0));
-        ls.ctl.rec = crlot::LaunchRecord{};  // (the record lists the last slice's launches)
-        rc = stft_impl(p, d_x + s0 * ld_x, spec_in, ns, T, ld_x, F, F * row, row, in_staged ? work : nullptr, s);
-        if (rc != CRLOT_OK) return rc;
-        int n_chunks = 1, m = 0;
-        crlot::phase_voc_chunks(ns, bins, Fp, n_chunks, m);
-        const crlot::PhaseVocArgs a{spec_in, spec_out, F * row, row, Fp * row, row, F, Fp, rate, ns, bins};
-        rc = phase_voc_run(a, n_chunks, m, sums, s);
-        if (rc != CRLOT_OK) return rc;
-        crlot::SpecMask mask = p->mask;
-        if (mask.p) mask.p += s0 * mask.ld_stream;
-        rc = istft_impl(p, spec_out, d_y + s0 * ld_y, ns, Fp, Fp * row, row, ld_y, out_staged ? work : nullptr,
-                        out_staged ? work + int64_t(ns) * Fp * row : nullptr, s, &mask);
-        if (rc != CRLOT_OK) return rc;
-    }
-    return CRLOT_OK;
+    const PitchTail tail{r, d_y, ld_y};
+    return time_stretch_locked(p, ls, d_x, nullptr, n_streams, T, F, Fp, rate, ld_x, 0, s, &tail);
 }
 
 }  // extern "C"

@@ -529,6 +529,37 @@ void phase_voc_chunks(int n_streams, int bins, int64_t Fp, int& n_chunks, int& m
 // k_phase_voc, after k_phase_voc_sums when n_chunks > 1 (sums: n_streams n_chunks bins int32)
 hipError_t launch_phase_voc(const PhaseVocArgs& a, int n_chunks, int m, int32_t* sums, hipStream_t s);
 
+// ---- resample.hip: the polyphase resampler (crlot_resample; the contract is in include/crlot_dsp.h)
+// x [n_streams][ld_x], T samples each -> y [n_streams][ld_y], n_out outputs each:
+// outputs below L = ceil(T U / D) are filtered, those in [L, n_out) stored as +0
+// (crlot_pitch_shift's fix_length).  table: device [U][K], K = 2 W; table_phase: the
+// same rows as the phase kernel's lanes load them, [K][U] with column r holding row
+// (r D) mod U, so a wave's loads of one tap are contiguous (null: no phase kernel).
+struct ResampleArgs {
+    const float* x;
+    float* y;
+    const float* table;
+    const float* table_phase;
+    int64_t ld_x, ld_y, T, L, n_out;
+    int32_t U, D, W, K;
+    int32_t n_streams;
+};
+constexpr int kResampleAuto = 0, kResamplePhase = 1, kResampleAny = 2;
+// does K_resample_phase take the shape (taps within its register buckets, U within
+// one workgroup, one block's input span within the tile's LDS budget)
+bool resample_phase_supported(int U, int D, int K);
+// route: kResample*; tile_blocks: output blocks of U per tile (0: the launcher's
+// choice).  Fills *rec with what it launched.  hipErrorNotSupported: kResamplePhase
+// on a shape K_resample_phase cannot take; hipErrorInvalidValue: a grid beyond 2^31-1.
+hipError_t launch_resample(const ResampleArgs& a, int route, int tile_blocks, crlot_resample_launch* rec,
+                           hipStream_t s);
+// resample_host.cpp: crlot_resample's body for a caller that has checked the arguments
+// (crlot_pitch_shift: n_out = T); takes the resampler's lock
+int resample_run(crlot_resampler* r, const float* d_x, float* d_y, int32_t n_streams, int64_t T, int64_t n_out,
+                 int64_t ld_x, int64_t ld_y, hipStream_t s);
+// the resampler's reduced rates and device (crlot_pitch_shift's checks)
+void resampler_rates(const crlot_resampler* r, int32_t& U, int32_t& D, int32_t& device);
+
 // dsp::FrameQueue frames on the device: [stream][F][N] from x [stream][ld_x]
 hipError_t launch_fq_frames(const float* x, int64_t T, int64_t ld_x, int n_streams, float* frames, int64_t F,
                             int64_t N, int64_t H, int64_t pad, int pad_mode, hipStream_t s);

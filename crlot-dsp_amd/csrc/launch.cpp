@@ -177,6 +177,8 @@ extern "C" const char* crlot_kernel_name(int32_t id) {
         case CRLOT_K_FEAT_STEP: return "k_feat_step";
         case CRLOT_K_PHASE_VOC: return "k_phase_voc";
         case CRLOT_K_PHASE_VOC_SUMS: return "k_phase_voc_sums";
+        case CRLOT_K_RESAMPLE_PHASE: return "k_resample_phase";
+        case CRLOT_K_RESAMPLE_ANY: return "k_resample_any";
         case CRLOT_K_EXPERIMENT: return "k_experiment";
         default: return "unknown";
     }

@@ -233,6 +233,8 @@ int crlot_test_inject(int32_t what, int32_t count);
 #define CRLOT_K_FEAT_STEP 34     /* crlot_spectrogram, staged: features of spectra in HBM */
 #define CRLOT_K_PHASE_VOC 35     /* crlot_phase_vocoder: spectra -> time-stretched spectra */
 #define CRLOT_K_PHASE_VOC_SUMS 36 /* ... the per-chunk phase increment sums, ahead of it when the walk is chunked */
+#define CRLOT_K_RESAMPLE_PHASE 37 /* crlot_resample: one lane per filter phase, its taps in registers */
+#define CRLOT_K_RESAMPLE_ANY 38  /* crlot_resample: one lane per output, any filter length */
 #define CRLOT_K_EXPERIMENT 99    /* experiment builds only */
 typedef struct crlot_launch_info {
     int32_t n_kernels;
@@ -513,6 +515,131 @@ int crlot_phase_vocoder(crlot_plan* plan, const float* d_spec_in, float* d_spec_
                         int64_t ld_spec_out, int64_t ld_frame_out, void* stream);
 int crlot_time_stretch(crlot_plan* plan, const float* d_x, float* d_y, int32_t n_streams, int64_t T,
                        double rate, int64_t ld_x, int64_t ld_y, void* stream);
+/* ---------------------------------------------------------------- resample / pitch shift
+ * A batched, band-limited rational resampler: the polyphase windowed-sinc design
+ * of torchaudio.functional.resample, from rate `down` to rate `up`.
+ *
+ * Object.  crlot_resampler_create checks the descriptor, builds the table on the
+ * host and touches no device; the table is uploaded to desc.device by the first
+ * call that needs it (a blocking copy; crlot_resampler_prepare does it ahead of
+ * time, e.g. before a stream capture).  The object is standalone: it needs no
+ * plan.  It is thread-safe behind its own mutex, as plans are.
+ *   up, down   new and original rate, both >= 1
+ *   zeros      1..64: zero crossings of the sinc kept on either side
+ *   rolloff    in [0.5, 1]: the cutoff as a share of the lower Nyquist rate
+ *   window     CRLOT_RESAMPLE_HANN or CRLOT_RESAMPLE_KAISER
+ *   beta       Kaiser only: finite, in [0, 20]
+ *   device     device index, >= 0
+ * Reduction and limits.  U = up / gcd and D = down / gcd must both lie in
+ * 1..4096 and U / D in [1/64, 64]; anything else is CRLOT_EINVAL.
+ * Filter geometry.  base = min(U, D) * rolloff, W = ceil(zeros * D / base),
+ * K = 2 W taps.  A table of more than 2^21 floats (U * K) is CRLOT_EUNSUPPORTED.
+ * Table.  The host builds it in double and rounds each entry once to float32:
+ *   h[r][i] for r in [0, U), i in [0, K):  j = i - W + 1,  tau = (j - r/U) * base / D,
+ *   h = (base / D) * sinc(tau) * win(tau) where |tau| < zeros, +0 elsewhere;
+ *   sinc(tau) = sin(pi tau) / (pi tau), 1 at tau = 0;
+ *   Hann:   win = cos^2(pi tau / (2 zeros));
+ *   Kaiser: win = I0(beta * sqrt(1 - (tau / zeros)^2)) / I0(beta).
+ * crlot_resampler_table copies the U x K table, row-major, to host memory;
+ * crlot_resample_table_host builds it from a descriptor without an object.
+ * Length.  L = crlot_resample_output_length(r, T) = (T * U + D - 1) div D; T = 0
+ * gives 0; T < 0 or T > 2^48 is CRLOT_EINVAL.
+ * Values.  For output m of a stream:
+ *   c = (m * D) div U and r = (m * D) mod U, in 64-bit integers;
+ *   acc = +0; for i = 0 .. K-1, in that order: acc = fmaf(h[r][i], xs[c - W + 1 + i], acc);
+ *   y[m] = acc + (+0.0f)   (a zero output is always +0, so an implementation that
+ *                           pads the table with zero taps stays bit-identical);
+ *   xs[k] is x[k] sanitized as everywhere else in this library (NaN / Inf -> 0,
+ *   |v| < 1e-30 -> 0), and 0 for k outside [0, T): such samples are never loaded.
+ * Invariance.  Every output is an independent chain in a fixed order, so the
+ * output bits do not depend on the tiling, the batch, a stream's position, the
+ * leading dimensions or the route.
+ *
+ * crlot_resample writes d_y[s*ld_y + m] for m < L.  The buffers must not overlap
+ * (CRLOT_EINVAL); ld_x >= T; ld_y >= L when n_streams > 1.  T = 0 or
+ * n_streams = 0: CRLOT_OK, nothing written.  Addressing is 64-bit throughout:
+ * no 2^27 / 2^29 extent limits.  More than 2^31-1 workgroups in one call is
+ * CRLOT_EUNSUPPORTED.
+ *
+ * Kernels.  CRLOT_K_RESAMPLE_PHASE while a table row fits in registers (K <= 104,
+ * U <= 512 and one block's input span fits the tile's LDS budget): a lane owns
+ * one phase and walks the output blocks q of its tile, m = q U + r.
+ * CRLOT_K_RESAMPLE_ANY for every other shape: one lane per output.  Both stage
+ * the tile's input span in LDS, sanitized once, and run the same tap order.
+ * Test knobs: crlot_resampler_set_route (CRLOT_RESAMPLE_PHASE on a shape it
+ * cannot take: CRLOT_EUNSUPPORTED), crlot_resampler_set_tile (n output blocks of
+ * U outputs per tile, clamped to what the LDS budget holds; 0: the library's
+ * choice), crlot_resampler_last_launch (the object's last launch on any stream).
+ *
+ * crlot_rational_approx: the best rational num / den to `ratio` with
+ * den <= max_den, by continued fractions with the final semiconvergent choice:
+ * exactly Python's fractions.Fraction(ratio).limit_denominator(max_den).  Host
+ * only.  CRLOT_EINVAL: a non-finite or non-positive ratio, one outside
+ * [2^-31, 2^31), max_den < 1, or a numerator beyond 2^31-1.
+ *
+ * crlot_pitch_shift multiplies the pitch by D / U and keeps the length.  By
+ * definition, with rate = (double)U / (double)D:
+ *   z = crlot_time_stretch(x, rate), of length Ls = crlot_stretch_output_length(plan, T, rate);
+ *   y[m] = crlot_resample(z)[m] for m < min(L(Ls), T), +0 for the rest up to T
+ *   (librosa's fix_length), bit for bit.
+ * T outputs per stream; ld_x >= T, ld_y >= T when n_streams > 1.  A rate outside
+ * time stretch's [1/64, 64] is CRLOT_EINVAL, as is a plan and a resampler on
+ * different devices.  The plan's gain and stored mask apply to the stretched
+ * frames, exactly as in crlot_time_stretch.  z lives in the stream's scratch
+ * slot behind time stretch's workspace; streams go in slices so that the whole
+ * workspace stays within 256 MiB, or one stream's worth if that is more.
+ * crlot_plan_last_launch lists the last slice's time-stretch kernels followed by
+ * the resample kernel. */
+#define CRLOT_RESAMPLE_HANN 0
+#define CRLOT_RESAMPLE_KAISER 1
+#define CRLOT_RESAMPLE_AUTO 0
+#define CRLOT_RESAMPLE_PHASE 1
+#define CRLOT_RESAMPLE_ANY 2
+typedef struct crlot_resampler crlot_resampler;
+typedef struct crlot_resampler_desc {
+    int32_t up, down;
+    int32_t zeros;
+    int32_t window;
+    double rolloff;
+    double beta;
+    int32_t device;
+    int32_t reserved;
+} crlot_resampler_desc;
+typedef struct crlot_resampler_geometry {
+    int32_t up, down;     /* U, D: reduced */
+    int32_t half_width;   /* W */
+    int32_t taps;         /* K = 2 W */
+    int32_t phase_ok;     /* 1 when CRLOT_K_RESAMPLE_PHASE takes the shape */
+    int32_t device;
+} crlot_resampler_geometry;
+typedef struct crlot_resample_launch {
+    int32_t kernel;        /* CRLOT_K_RESAMPLE_PHASE / _ANY; 0: no launch yet */
+    int32_t threads;       /* per workgroup */
+    int64_t grid;          /* workgroups */
+    int64_t tile_outputs;  /* outputs per tile */
+    int32_t tile;          /* output blocks per tile (0: a tile is part of a block) */
+    int32_t groups;        /* phase kernel: groups of U phases per workgroup */
+    int32_t taps_padded;   /* phase kernel: the register bucket */
+    int32_t lds_table;     /* any kernel: 1 when the table is staged in LDS */
+    int64_t lds_bytes;
+} crlot_resample_launch;
+int crlot_resample_geometry(const crlot_resampler_desc* desc, crlot_resampler_geometry* out); /* host only */
+int crlot_resample_table_host(const crlot_resampler_desc* desc, float* out /* [U][K] */);     /* host only */
+int crlot_rational_approx(double ratio, int32_t max_den, int32_t* num, int32_t* den);         /* host only */
+int crlot_resampler_create(const crlot_resampler_desc* desc, crlot_resampler** out);
+void crlot_resampler_destroy(crlot_resampler* r);
+int crlot_resampler_info(const crlot_resampler* r, crlot_resampler_geometry* out);
+int crlot_resampler_table(const crlot_resampler* r, float* host_out /* [U][K] */);
+int crlot_resampler_prepare(crlot_resampler* r);
+int64_t crlot_resample_output_length(const crlot_resampler* r, int64_t T);
+int crlot_resampler_set_route(crlot_resampler* r, int32_t route);
+int crlot_resampler_set_tile(crlot_resampler* r, int32_t n_blocks);
+int crlot_resampler_last_launch(const crlot_resampler* r, crlot_resample_launch* out);
+int crlot_resample(crlot_resampler* r, const float* d_x, float* d_y, int32_t n_streams, int64_t T,
+                   int64_t ld_x, int64_t ld_y, void* stream);
+int crlot_pitch_shift(crlot_plan* plan, crlot_resampler* r, const float* d_x, float* d_y, int32_t n_streams,
+                      int64_t T, int64_t ld_x, int64_t ld_y, void* stream);
+
 /* host helpers (no device) */
 #define CRLOT_MEL_HTK 0
 #define CRLOT_MEL_SLANEY 1

@@ -110,6 +110,67 @@ class Plan {
     crlot_plan* p_ = nullptr;
 };
 
+// Band-limited rational resampler from rate `down` to rate `up` (crlot_resampler_*):
+// the polyphase windowed-sinc filter of torchaudio.functional.resample.  Needs no plan.
+class Resampler {
+   public:
+    Resampler(int up, int down, int zeros = 16, double rolloff = 0.95, int window = CRLOT_RESAMPLE_HANN,
+              double beta = 8.6, int device = 0) {
+        crlot_resampler_desc d{};
+        d.up = up;
+        d.down = down;
+        d.zeros = zeros;
+        d.window = window;
+        d.rolloff = rolloff;
+        d.beta = beta;
+        d.device = device;
+        check(crlot_resampler_create(&d, &r_), "crlot_resampler_create");
+    }
+    ~Resampler() { crlot_resampler_destroy(r_); }
+    Resampler(const Resampler&) = delete;
+    Resampler& operator=(const Resampler&) = delete;
+    Resampler(Resampler&& o) noexcept : r_(o.r_) { o.r_ = nullptr; }
+    Resampler& operator=(Resampler&& o) noexcept {
+        if (this != &o) {
+            crlot_resampler_destroy(r_);
+            r_ = o.r_;
+            o.r_ = nullptr;
+        }
+        return *this;
+    }
+    // the best num / den to ratio with den <= max_den (fractions.Fraction.limit_denominator)
+    static std::pair<int, int> rational_approx(double ratio, int max_den) {
+        int32_t n = 0, d = 0;
+        check(crlot_rational_approx(ratio, max_den, &n, &d), "crlot_rational_approx");
+        return {n, d};
+    }
+    crlot_resampler_geometry info() const {
+        crlot_resampler_geometry g{};
+        check(crlot_resampler_info(r_, &g), "crlot_resampler_info");
+        return g;
+    }
+    int64_t output_length(int64_t T) const {
+        const int64_t L = crlot_resample_output_length(r_, T);
+        check(L < 0 ? int(L) : 0, "crlot_resample_output_length");
+        return L;
+    }
+    std::vector<float> table() const {
+        const crlot_resampler_geometry g = info();
+        std::vector<float> t(size_t(g.up) * g.taps);
+        check(crlot_resampler_table(r_, t.data()), "crlot_resampler_table");
+        return t;
+    }
+    // d_x [n_streams][ld_x], T samples each -> d_y [n_streams][ld_y], output_length(T) each; no overlap
+    void resample_device(const float* d_x, float* d_y, int n_streams, int64_t T, int64_t ld_x, int64_t ld_y,
+                         hipStream_t s = nullptr) {
+        check(crlot_resample(r_, d_x, d_y, n_streams, T, ld_x, ld_y, s), "crlot_resample");
+    }
+    crlot_resampler* get() const { return r_; }
+
+   private:
+    crlot_resampler* r_ = nullptr;
+};
+
 // Batched round trip: n_streams mono streams, each T samples.
 class StftEngine {
    public:
@@ -191,6 +252,12 @@ class StftEngine {
     void time_stretch_device(const float* d_x, float* d_y, int n_streams, int64_t T, double rate, int64_t ld_x,
                              int64_t ld_y, hipStream_t s = nullptr) {
         check(crlot_time_stretch(plan_.get(), d_x, d_y, n_streams, T, rate, ld_x, ld_y, s), "crlot_time_stretch");
+    }
+    // Pitch multiplied by down / up of `r` at the same length: resample(time_stretch(x, up / down))
+    // cropped or zero-filled to T samples per stream (crlot_pitch_shift); r on the plan's device
+    void pitch_shift_device(Resampler& r, const float* d_x, float* d_y, int n_streams, int64_t T, int64_t ld_x,
+                            int64_t ld_y, hipStream_t s = nullptr) {
+        check(crlot_pitch_shift(plan_.get(), r.get(), d_x, d_y, n_streams, T, ld_x, ld_y, s), "crlot_pitch_shift");
     }
     // per-frame real mask rows of bins(): frame k of stream s at d_mask + s*ld_stream + k*ld_frame
     // (ld_stream 0: one mask shared by the streams); nullptr clears it
