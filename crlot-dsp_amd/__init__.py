@@ -170,6 +170,9 @@ def lib():
         "crlot_stretch_output_length": ([vp, i64, C.c_double], i64),
         "crlot_phase_vocoder": ([vp, vp, vp, i32, i64, C.c_double, i64, i64, i64, i64, vp], C.c_int),
         "crlot_time_stretch": ([vp, vp, vp, i32, i64, C.c_double, i64, i64, vp], C.c_int),
+        "crlot_gl_project": ([vp, vp, vp, vp, vp, i32, i64, C.c_double, i64, i64, i64, i64, i64, i64, i64, i64, vp],
+                             C.c_int),
+        "crlot_griffin_lim": ([vp, vp, i64, i64, vp, i64, i64, vp, i64, i32, i64, i32, C.c_double, vp], C.c_int),
         "crlot_resample_geometry": ([C.POINTER(ResamplerDesc), C.POINTER(ResamplerGeometry)], C.c_int),
         "crlot_resample_table_host": ([C.POINTER(ResamplerDesc), fp], C.c_int),
         "crlot_rational_approx": ([C.c_double, i32, C.POINTER(i32), C.POINTER(i32)], C.c_int),
@@ -478,6 +481,65 @@ def _stretch_spec_layout(shape, strides, dtype: str, device_index, plan_device: 
     return 2 * ld_spec, 2 * ld_frame
 
 
+def _gl_mag_layout(shape, strides, dtype: str, device_index, plan_device: int, bins: int, what: str = "mag",
+                   expect=None):
+    """Validate a magnitude tensor of Plan.gl_project / Plan.griffin_lim from its
+    plain description (shape and strides in elements as tuples, dtype name, device
+    index or None for a host tensor): (S, F, bins) float32 on the plan's device, rows
+    contiguous and at least `bins` apart, streams not overlapping; `expect`: the
+    (S, F, bins) it must have.  Returns (S, F, ld_mag, ld_frame)."""
+    shape, strides = tuple(int(v) for v in shape), tuple(int(v) for v in strides)
+    if len(shape) != 3 or len(strides) != 3 or shape[2] != bins:
+        raise ValueError(f"{what} must be (S, F, N/2+1) or (F, N/2+1) float32")
+    if expect is not None and shape != tuple(expect):
+        raise ValueError(f"{what} must be {tuple(expect)}, not {shape}")
+    if dtype != "float32":
+        raise ValueError(f"{what} must be float32, not {dtype}")
+    if device_index is None or int(device_index) != int(plan_device):
+        raise ValueError(f"{what} must live on the plan's device {plan_device}, not "
+                         f"{'the host' if device_index is None else device_index}")
+    if strides[2] != 1:
+        raise ValueError(f"{what} must have contiguous rows")
+    S, F = shape[0], shape[1]
+    # a size-1 dim's stride is meaningless: the dense value there
+    ld_frame = strides[1] if F > 1 else bins
+    ld_mag = strides[0] if S > 1 else max(F, 1) * ld_frame
+    if ld_frame < bins:
+        raise ValueError(f"{what} rows overlap: ld_frame < N/2+1")
+    if S > 1 and ld_mag < (F - 1) * ld_frame + bins:
+        raise ValueError(f"{what} streams overlap: the stream stride is too small")
+    return S, F, ld_mag, ld_frame
+
+
+def _gl_y_layout(shape, strides, dtype: str, device_index, plan_device: int, S: int, L: int):
+    """The same for Plan.griffin_lim's output: (S, >= L) float32 on the plan's
+    device, rows contiguous and not overlapping.  Returns ld_y."""
+    shape, strides = tuple(int(v) for v in shape), tuple(int(v) for v in strides)
+    if len(shape) != 2 or len(strides) != 2 or shape[0] != S or shape[1] < L:
+        raise ValueError(f"y must be ({S}, >= {L})")
+    if dtype != "float32":
+        raise ValueError(f"y must be float32, not {dtype}")
+    if device_index is None or int(device_index) != int(plan_device):
+        raise ValueError(f"y must live on the plan's device {plan_device}, not "
+                         f"{'the host' if device_index is None else device_index}")
+    if shape[1] > 1 and strides[1] != 1:
+        raise ValueError("y must have contiguous rows")
+    ld_y = strides[0] if S > 1 else max(L, 1)
+    if S > 1 and ld_y < L:
+        raise ValueError("y rows overlap: the stream stride is below F * H")
+    return ld_y
+
+
+def _gl_scalars(n_iter: int, momentum: float):
+    """n_iter in [0, 65536] and a finite momentum in [0, 1), else ValueError."""
+    if int(n_iter) != n_iter or not 0 <= int(n_iter) <= 65536:
+        raise ValueError("n_iter must be an integer in [0, 65536]")
+    m = float(momentum)
+    if not (m == m and 0.0 <= m < 1.0):
+        raise ValueError("momentum must be finite and in [0, 1)")
+    return int(n_iter), m
+
+
 def _stream_handle(tensor) -> int:
     torch = _torch()
     return int(torch.cuda.current_stream(tensor.device).cuda_stream)
@@ -703,6 +765,62 @@ class Plan:
         s = _stream_handle(x) if stream is None else stream
         _check(lib().crlot_time_stretch(self._h, x.data_ptr(), y.data_ptr(), S, T, float(rate), _ld(x, 0, T),
                                         _ld(y, 0, L), s), "crlot_time_stretch")
+        return y
+
+    def gl_project(self, spec, mag, tprev=None, momentum: float = 0.0, out=None, stream: int | None = None):
+        """The Griffin-Lim projection (crlot_gl_project): spec, tprev (optional, the
+        previous rebuilt spectra), out: (S, F, N/2+1) or (F, N/2+1) complex64, mag the
+        same shape in float32 -> out = mag * c / (|c| + 1e-16), c = spec - tprev *
+        momentum / (1 + momentum).  out may be spec itself (in place)."""
+        if len(spec.shape) == 2:
+            return self.gl_project(spec[None], mag[None] if len(mag.shape) == 2 else mag,
+                                   None if tprev is None else tprev[None], momentum,
+                                   None if out is None else out[None], stream)[0]
+        _, m = _gl_scalars(0, momentum)
+        bins, dev = self.frame_size // 2 + 1, self._device_index()
+        ld_s, ldf_s = _stretch_spec_layout(*_tensor_layout(spec), dev, bins)
+        S, F = int(spec.shape[0]), int(spec.shape[1])
+        _, _, ld_m, ldf_m = _gl_mag_layout(*_tensor_layout(mag), dev, bins, "mag", (S, F, bins))
+        ld_t = ldf_t = 0
+        if tprev is not None:
+            ld_t, ldf_t = _stretch_spec_layout(*_tensor_layout(tprev), dev, bins, "tprev", (S, F, bins))
+        if out is None:
+            out = _torch().empty((S, F, bins), dtype=spec.dtype, device=spec.device)
+        ld_o, ldf_o = _stretch_spec_layout(*_tensor_layout(out), dev, bins, "out", (S, F, bins))
+        s = _stream_handle(spec) if stream is None else stream
+        _check(lib().crlot_gl_project(self._h, spec.data_ptr(), None if tprev is None else tprev.data_ptr(),
+                                      mag.data_ptr(), out.data_ptr(), S, F, m, ld_s, ldf_s, ld_t, ldf_t, ld_m, ldf_m,
+                                      ld_o, ldf_o, s), "crlot_gl_project")
+        return out
+
+    def griffin_lim(self, mag, n_iter: int = 32, momentum: float = 0.99, init=None, y=None,
+                    stream: int | None = None):
+        """mag: (S, F, N/2+1) or (F, N/2+1) float32 device tensor of target magnitudes
+        -> y: (S, F * H), the signal whose STFT magnitudes approach mag after n_iter
+        fast Griffin-Lim iterations (crlot_griffin_lim; librosa / torchaudio
+        GriffinLim).  init: optional complex64 spectra of the same shape giving the
+        starting phases (default: zero phase).  The plan must use ZERO_PAD framing
+        and have no spectral gain or mask.  On a default plan, whose norm table is
+        the sum of the window, the magnitudes of y settle at sum(w^2) / sum(w) times
+        mag (the phases are reconstructed, the level is not); for magnitudes that
+        approach mag, upload_tables(norm=sum of w^2 per sample, ring_len floats)
+        first (include/crlot_dsp.h, "What it converges to")."""
+        if len(mag.shape) == 2:
+            return self.griffin_lim(mag[None], n_iter, momentum, None if init is None else init[None],
+                                    None if y is None else y[None], stream)[0]
+        n_iter, m = _gl_scalars(n_iter, momentum)
+        bins, dev = self.frame_size // 2 + 1, self._device_index()
+        S, F, ld_m, ldf_m = _gl_mag_layout(*_tensor_layout(mag), dev, bins)
+        ld_i = ldf_i = 0
+        if init is not None:
+            ld_i, ldf_i = _stretch_spec_layout(*_tensor_layout(init), dev, bins, "init", (S, F, bins))
+        L = F * self.hop_size
+        if y is None:
+            y = _torch().empty((S, L), dtype=mag.dtype, device=mag.device)
+        ld_y = _gl_y_layout(*_tensor_layout(y), dev, S, L)
+        s = _stream_handle(mag) if stream is None else stream
+        _check(lib().crlot_griffin_lim(self._h, mag.data_ptr(), ld_m, ldf_m, None if init is None else init.data_ptr(),
+                                       ld_i, ldf_i, y.data_ptr(), ld_y, S, F, n_iter, m, s), "crlot_griffin_lim")
         return y
 
     def pitch_shift(self, x, resampler=None, semitones: float | None = None, max_den: int = 256, y=None,

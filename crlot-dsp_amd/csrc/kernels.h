@@ -560,6 +560,38 @@ int resample_run(crlot_resampler* r, const float* d_x, float* d_y, int32_t n_str
 // the resampler's reduced rates and device (crlot_pitch_shift's checks)
 void resampler_rates(const crlot_resampler* r, int32_t& U, int32_t& D, int32_t& device);
 
+// ---- griffin_lim.hip: Griffin-Lim (crlot_gl_project / crlot_griffin_lim; the contract is in include/crlot_dsp.h)
+// Spectra rows of `bins` float pairs and magnitude rows of `bins` floats, frame k of
+// stream s at p + s ld + k ldf on every operand; tprev nullable (absent); out may be spec.
+struct GlProjectArgs {
+    const float* spec;
+    const float* tprev;
+    const float* mag;
+    float* out;
+    int64_t ld_spec, ldf_spec, ld_tprev, ldf_tprev, ld_mag, ldf_mag, ld_out, ldf_out;
+    int64_t F;
+    int32_t n_streams, bins;
+    float alpha;  // (float)(momentum / (1 + momentum))
+};
+hipError_t launch_gl_project(const GlProjectArgs& a, hipStream_t s);
+// One fused iteration y_in -> y_out (F H samples per stream, never in place) at
+// gl_iter_supported's shapes (istft_walk_supported with N <= 1024, fewer with momentum); also needs the
+// exact-rewrite tables, ring_len % H == 0, no padding and 8-byte aligned y_out rows.
+// tprev (nullable): the previous rebuilt spectra; tnew (nullable): receives this
+// iteration's, rows of N + 2 floats or more.  Chunks by K_istft's policy, recorded.
+struct GlIterArgs {
+    const float* y_in;
+    float* y_out;
+    const float* mag;
+    const float* tprev;
+    float* tnew;
+    int64_t ld_in, ld_out, ld_mag, ldf_mag, ld_tprev, ldf_tprev, ld_tnew, ldf_tnew;
+    float alpha;
+};
+bool gl_iter_supported(int n, int h, bool momentum);
+hipError_t launch_gl_iter(const Geometry& g, const DevTables& t, const GlIterArgs& a, int n_streams, int64_t F,
+                          hipStream_t s);
+
 // dsp::FrameQueue frames on the device: [stream][F][N] from x [stream][ld_x]
 hipError_t launch_fq_frames(const float* x, int64_t T, int64_t ld_x, int n_streams, float* frames, int64_t F,
                             int64_t N, int64_t H, int64_t pad, int pad_mode, hipStream_t s);

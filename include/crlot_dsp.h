@@ -235,6 +235,8 @@ int crlot_test_inject(int32_t what, int32_t count);
 #define CRLOT_K_PHASE_VOC_SUMS 36 /* ... the per-chunk phase increment sums, ahead of it when the walk is chunked */
 #define CRLOT_K_RESAMPLE_PHASE 37 /* crlot_resample: one lane per filter phase, its taps in registers */
 #define CRLOT_K_RESAMPLE_ANY 38  /* crlot_resample: one lane per output, any filter length */
+#define CRLOT_K_GL_PROJECT 39   /* crlot_gl_project: the Griffin-Lim projection over spectra in HBM */
+#define CRLOT_K_GL_ITER 40      /* crlot_griffin_lim: one fused iteration y_i -> y_i+1 (N = 256 / 512 / 1024) */
 #define CRLOT_K_EXPERIMENT 99    /* experiment builds only */
 typedef struct crlot_launch_info {
     int32_t n_kernels;
@@ -639,6 +641,101 @@ int crlot_resample(crlot_resampler* r, const float* d_x, float* d_y, int32_t n_s
                    int64_t ld_x, int64_t ld_y, void* stream);
 int crlot_pitch_shift(crlot_plan* plan, crlot_resampler* r, const float* d_x, float* d_y, int32_t n_streams,
                       int64_t T, int64_t ld_x, int64_t ld_y, void* stream);
+
+/* ---------------------------------------------------------------- Griffin-Lim
+ * From magnitudes back to audio: the fast Griffin-Lim iteration of librosa.griffinlim
+ * / torchaudio.transforms.GriffinLim around the plan's crlot_stft and
+ * crlot_istft_ola.
+ *
+ * The projection, per stream, frame and bin.  X is the rebuilt spectrum, T the
+ * previous rebuilt spectrum (absent on the first iteration or with momentum 0),
+ * m the target magnitude.  Every operation is one correctly rounded float32
+ * operation, no FMA:
+ *   alpha = (float)((double)momentum / (1.0 + (double)momentum))      momentum in [0, 1)
+ *   c   = (X.re - fl(alpha*T.re), X.im - fl(alpha*T.im))              (c = X when T is absent)
+ *   p   = fl(fl(c.re*c.re) + fl(c.im*c.im))
+ *   d   = fl(sqrtf(p) + 1e-16f)                                       sqrtf correctly rounded
+ *   s   = m / d                                                       IEEE division
+ *   out = (fl(c.re*s), fl(c.im*s))
+ * X and T are sanitized on load as IFftPlan's sanitize does (NaN / Inf -> 0,
+ * |v| < 1e-30 -> 0), and so is m; a negative m is used as it is.  Bins 0 and N/2
+ * take the imaginary parts of X and T as 0 and store +0.  This is torchaudio's /
+ * librosa's update, angles = rebuilt - tprev * momentum / (1 + momentum);
+ * angles /= |angles| + 1e-16; spec = mag * angles, with one division instead of two.
+ * Domain: exact to float32 rounding for components of c in {0} or [2^-60, 2^60]
+ * in size and m within [2^-60, 2^60] or 0; beyond that c.re*c.re + c.im*c.im may
+ * overflow (s = 0) or underflow (d = 1e-16, s up to 1e16 m).
+ *
+ * crlot_gl_project applies the projection over spectra in crlot_stft's layout:
+ * bin b of frame k of stream s at d[s*ld + k*ld_frame + 2*b] for d_spec, d_tprev
+ * (NULL: absent) and d_out, at d_mag[s*ld_mag + k*ld_frame_mag + b] for the
+ * magnitudes; every operand has its own leading dimensions; ld_frame >= N+2
+ * floats for spectra (even leading dimensions, 8-byte aligned bases), >= N/2+1 for
+ * d_mag.  d_out may be exactly d_spec with d_spec's leading dimensions (in
+ * place); any other overlap of d_out with an input is CRLOT_EINVAL.  momentum
+ * must be finite and in [0, 1).  F = 0 or n_streams = 0: CRLOT_OK, nothing
+ * written.  One lane per (stream, frame, bin), 64-bit addressing
+ * (CRLOT_K_GL_PROJECT).
+ *
+ * crlot_griffin_lim: S_0 = d_mag + 0i when d_init is NULL (the magnitudes as
+ * stored: this one path does not sanitize m), else project(d_init, absent, d_mag);
+ * then
+ *   y_0     = istft_ola(S_0)
+ *   y_{i+1} = istft_ola(project(stft(y_i), tprev_i, mag)),   tprev_{i+1} = stft(y_i)
+ * for n_iter iterations (tprev_0 absent; with momentum 0 always absent), and
+ * d_y[s*ld_y + n] = y_{n_iter}[n] for n < F*H.  It is by definition that
+ * composition of crlot_istft_ola, crlot_stft (on F*H samples per stream) and
+ * crlot_gl_project on the plan.  n_iter in [0, 65536]; momentum finite, in
+ * [0, 1); the plan must frame with CRLOT_ZERO_PAD (the only mode in which
+ * crlot_frame_count(F*H) == F, so the loop is closed; other modes:
+ * CRLOT_EUNSUPPORTED) and must have no spectral gain and no stored mask, because
+ * the projection is the spectral step (CRLOT_EINVAL otherwise).  d_init is in
+ * crlot_stft's layout.  F = 0 or n_streams = 0: CRLOT_OK, nothing written.
+ *
+ * What it converges to.  Griffin and Lim's theorem (the distance between |stft(y_i)|
+ * and d_mag never increases) holds for the least-squares inverse, whose overlap-add
+ * is divided by the sum of w^2 over the frames covering a sample.  A default plan
+ * divides by the reference's table, the sum of w, so with an analysis window
+ * istft_ola(stft(x)) = x sum(w^2) / sum(w), every y_i is the least-squares
+ * iteration's scaled by that factor (the projection reads phases only), and the
+ * relative distance settles near 1 - sum(w^2) / sum(w) (0.25 for Hann at 75 %
+ * overlap) instead of falling towards 0: the phases are reconstructed, the level
+ * is not.  For magnitudes that approach d_mag upload sum(w^2) as the plan's norm
+ * table first (crlot_plan_upload_tables; ring_len floats, periodic in H).
+ *
+ * Kernels.  At N = 256 / 512 / 1024 with H a multiple of 128 dividing N (and
+ * ring_len % H == 0, the default) an iteration is one launch, CRLOT_K_GL_ITER:
+ * K_istft's walk from y_i with the projection as its step; with momentum 0 no
+ * spectrum reaches memory.  crlot_plan_set_chunks forces its chunking.  N = 1024
+ * at H = 128 and 512 with momentum > 0 is not among these "fused shapes": the
+ * walk measured slower than the staged iteration there.  Every other shape runs crlot_stft's dispatch, CRLOT_K_GL_PROJECT and
+ * crlot_istft_ola's dispatch per iteration.  y_0 is crlot_istft_ola's dispatch.
+ * Workspace (the stream's scratch slot): two y buffers, S_0 and, with momentum,
+ * two rebuilt spectra, one of them in S_0's place (staged shapes: S_0's buffer holds
+ * the projected rows, two more the rebuilt ones, and the staged routes' frames);
+ * the streams are processed in slices whose workspace stays within 256 MiB, or
+ * one stream's worth if that is more, and a slice runs all its iterations before
+ * the next one starts.  crlot_plan_last_launch lists the kernels of the last
+ * iteration of the last slice (of y_0 when n_iter is 0).
+ *
+ * Bits.  With frame pairing off the result equals the composition of the three
+ * public entries bit for bit at every shape.  At the fused shapes the result does
+ * not depend on the pairing setting (the walk, and y_0 there, are per-frame
+ * arithmetic): with pairing on it equals the pairing-off composition bit for bit.
+ * At the other shapes it equals the composition under the plan's own pairing
+ * setting.  The bits never depend on chunking, the batch size, a stream's
+ * position in the batch, slicing, the leading dimensions or the alignment of
+ * d_y: the last step writes d_y itself only where crlot_istft_ola's dispatch takes
+ * the same route into d_y as into the workspace (8-byte aligned rows an even
+ * distance apart), and otherwise through the workspace.  With n_streams == 1,
+ * ld_y is not read. */
+int crlot_gl_project(crlot_plan* plan, const float* d_spec, const float* d_tprev, const float* d_mag, float* d_out,
+                     int32_t n_streams, int64_t F, double momentum, int64_t ld_spec, int64_t ld_frame_spec,
+                     int64_t ld_tprev, int64_t ld_frame_tprev, int64_t ld_mag, int64_t ld_frame_mag,
+                     int64_t ld_out, int64_t ld_frame_out, void* stream);
+int crlot_griffin_lim(crlot_plan* plan, const float* d_mag, int64_t ld_mag, int64_t ld_frame_mag,
+                      const float* d_init, int64_t ld_init, int64_t ld_frame_init, float* d_y, int64_t ld_y,
+                      int32_t n_streams, int64_t F, int32_t n_iter, double momentum, void* stream);
 
 /* host helpers (no device) */
 #define CRLOT_MEL_HTK 0

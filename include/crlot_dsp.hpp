@@ -259,6 +259,28 @@ class StftEngine {
                             int64_t ld_y, hipStream_t s = nullptr) {
         check(crlot_pitch_shift(plan_.get(), r.get(), d_x, d_y, n_streams, T, ld_x, ld_y, s), "crlot_pitch_shift");
     }
+    // The Griffin-Lim projection over spectra in stft_device's layout (crlot_gl_project): d_tprev may be
+    // null (absent), d_out may be d_spec (in place); mag rows of bins() floats.  Dense layouts when the
+    // leading dimensions are 0: rows of 2 * bins() floats (bins() for d_mag), F rows per stream.
+    void gl_project_device(const float* d_spec, const float* d_tprev, const float* d_mag, float* d_out, int n_streams,
+                           int64_t F, double momentum, int64_t ld_spec = 0, int64_t ld_frame = 0, int64_t ld_mag = 0,
+                           int64_t ld_frame_mag = 0, hipStream_t s = nullptr) {
+        const int64_t lf = ld_frame ? ld_frame : 2 * int64_t(bins()), ls = ld_spec ? ld_spec : F * lf;
+        const int64_t lfm = ld_frame_mag ? ld_frame_mag : bins(), lm = ld_mag ? ld_mag : F * lfm;
+        check(crlot_gl_project(plan_.get(), d_spec, d_tprev, d_mag, d_out, n_streams, F, momentum, ls, lf, ls, lf, lm,
+                               lfm, ls, lf, s),
+              "crlot_gl_project");
+    }
+    // Magnitudes -> audio by n_iter fast Griffin-Lim iterations (crlot_griffin_lim): d_mag [n_streams][F][bins()]
+    // dense, d_init (nullable) the starting spectra [n_streams][F][bins()] complex, d_y [n_streams][ld_y], F * hop
+    // samples each.  ZERO_PAD plans without a spectral gain or mask.
+    void griffin_lim_device(const float* d_mag, const float* d_init_or_null, float* d_y, int n_streams, int64_t F,
+                            int n_iter, double momentum, int64_t ld_y, hipStream_t s = nullptr) {
+        const int64_t b = bins();
+        check(crlot_griffin_lim(plan_.get(), d_mag, F * b, b, d_init_or_null, 2 * F * b, 2 * b, d_y, ld_y, n_streams, F,
+                                n_iter, momentum, s),
+              "crlot_griffin_lim");
+    }
     // per-frame real mask rows of bins(): frame k of stream s at d_mask + s*ld_stream + k*ld_frame
     // (ld_stream 0: one mask shared by the streams); nullptr clears it
     void set_spectral_mask(const float* d_mask_or_null, int64_t ld_frame = 0, int64_t ld_stream = 0) {
