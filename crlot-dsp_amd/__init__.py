@@ -109,6 +109,12 @@ class ResampleLaunch(C.Structure):
                 ("lds_bytes", C.c_int64)]
 
 
+class HpssDesc(C.Structure):
+    """crlot_hpss_desc (include/crlot_dsp.h)."""
+    _fields_ = [("win_harm", C.c_int32), ("win_perc", C.c_int32), ("power", C.c_int32), ("reserved", C.c_int32),
+                ("margin_harm", C.c_double), ("margin_perc", C.c_double)]
+
+
 class FftDesc(C.Structure):
     """crlot_fft_desc (include/crlot_dsp.h)."""
     _fields_ = [("domain", C.c_int32), ("nfft", C.c_int32), ("device", C.c_int32)]
@@ -173,6 +179,8 @@ def lib():
         "crlot_gl_project": ([vp, vp, vp, vp, vp, i32, i64, C.c_double, i64, i64, i64, i64, i64, i64, i64, i64, vp],
                              C.c_int),
         "crlot_griffin_lim": ([vp, vp, i64, i64, vp, i64, i64, vp, i64, i32, i64, i32, C.c_double, vp], C.c_int),
+        "crlot_hpss_masks": ([vp, C.POINTER(HpssDesc), vp, vp, vp, i32, i64, i64, i64, i64, i64, i64, i64, vp], C.c_int),
+        "crlot_hpss": ([vp, C.POINTER(HpssDesc), vp, vp, vp, i32, i64, i64, i64, i64, vp], C.c_int),
         "crlot_resample_geometry": ([C.POINTER(ResamplerDesc), C.POINTER(ResamplerGeometry)], C.c_int),
         "crlot_resample_table_host": ([C.POINTER(ResamplerDesc), fp], C.c_int),
         "crlot_rational_approx": ([C.c_double, i32, C.POINTER(i32), C.POINTER(i32)], C.c_int),
@@ -540,6 +548,47 @@ def _gl_scalars(n_iter: int, momentum: float):
     return int(n_iter), m
 
 
+HPSS_HARD = -1  # crlot_hpss_desc.power: the hard masks (librosa's power = inf)
+
+
+def _hpss_desc(kernel_size=31, power=2, margin=1.0) -> HpssDesc:
+    """Plan.hpss / Plan.hpss_masks's scalars as a crlot_hpss_desc: kernel_size and
+    margin a scalar or a (harm, perc) pair as in librosa; windows odd in [1, 63];
+    power 1, 2 or inf (HPSS_HARD); margins finite and >= 1.  ValueError otherwise."""
+    def pair(v, what):
+        if isinstance(v, (tuple, list)):
+            if len(v) != 2:
+                raise ValueError(f"{what} must be a scalar or a (harm, perc) pair")
+            return v[0], v[1]
+        return v, v
+    wins = pair(kernel_size, "kernel_size")
+    for w in wins:
+        if isinstance(w, bool) or int(w) != w or not 1 <= int(w) <= 63 or int(w) % 2 == 0:
+            raise ValueError("kernel_size must be odd and in [1, 63]")
+    margins = tuple(float(m) for m in pair(margin, "margin"))
+    for m in margins:
+        if not (m == m and 1.0 <= m < float("inf")):
+            raise ValueError("margin must be finite and >= 1")
+    if power == float("inf") or power == HPSS_HARD:
+        pw = HPSS_HARD
+    elif power in (1, 2):
+        pw = int(power)
+    else:
+        raise ValueError("power must be 1, 2 or inf")
+    return HpssDesc(int(wins[0]), int(wins[1]), pw, 0, margins[0], margins[1])
+
+
+def _tensors_overlap(a, b) -> bool:
+    """Do the address ranges of two tensors (first to last element) intersect."""
+    def span(t):
+        last = sum((int(n) - 1) * int(st) for n, st in zip(t.shape, t.stride()))
+        return int(t.data_ptr()), int(t.data_ptr()) + (last + 1) * int(t.element_size())
+    if a.numel() == 0 or b.numel() == 0:
+        return False
+    (a0, a1), (b0, b1) = span(a), span(b)
+    return a0 < b1 and b0 < a1
+
+
 def _stream_handle(tensor) -> int:
     torch = _torch()
     return int(torch.cuda.current_stream(tensor.device).cuda_stream)
@@ -822,6 +871,82 @@ class Plan:
         _check(lib().crlot_griffin_lim(self._h, mag.data_ptr(), ld_m, ldf_m, None if init is None else init.data_ptr(),
                                        ld_i, ldf_i, y.data_ptr(), ld_y, S, F, n_iter, m, s), "crlot_griffin_lim")
         return y
+
+    def hpss_masks(self, spec, kernel_size=31, power=2, margin=1.0, mask_h=None, mask_p=None,
+                   stream: int | None = None):
+        """spec: (S, F, N/2+1) or (F, N/2+1) complex64 device tensor -> (mask_h, mask_p),
+        float32 of the same shape: the harmonic and percussive soft masks of
+        librosa.decompose.hpss(mask=True) (crlot_hpss_masks): medians of |spec| over
+        kernel_size frames and bins, margins and power as in librosa (power 1, 2 or
+        inf).  Pass mask_h=False or mask_p=False to skip that mask (None is returned
+        in its place); a tensor is written in place (rows may be padded).  The masks
+        are what Plan.set_spectral_mask takes."""
+        if len(spec.shape) == 2:
+            up = lambda m: m[None] if m is not None and m is not False else m  # noqa: E731
+            mh, mp = self.hpss_masks(spec[None], kernel_size, power, margin, up(mask_h), up(mask_p), stream)
+            return (None if mh is None else mh[0]), (None if mp is None else mp[0])
+        desc = _hpss_desc(kernel_size, power, margin)
+        if mask_h is False and mask_p is False:
+            raise ValueError("at least one of mask_h and mask_p must be computed")
+        bins, dev = self.frame_size // 2 + 1, self._device_index()
+        ld_s, ldf_s = _stretch_spec_layout(*_tensor_layout(spec), dev, bins)
+        S, F = int(spec.shape[0]), int(spec.shape[1])
+        outs, lds = [], []
+        for m, what in ((mask_h, "mask_h"), (mask_p, "mask_p")):
+            if m is False:
+                outs.append(None)
+                lds.append((0, 0))
+                continue
+            if m is None:
+                m = _torch().empty((S, F, bins), dtype=_torch().float32, device=spec.device)
+            _, _, ld_m, ldf_m = _gl_mag_layout(*_tensor_layout(m), dev, bins, what, (S, F, bins))
+            if _tensors_overlap(m, spec) or any(o is not None and _tensors_overlap(m, o) for o in outs):
+                raise ValueError(f"{what} overlaps spec or the other mask")
+            outs.append(m)
+            lds.append((ld_m, ldf_m))
+        s = _stream_handle(spec) if stream is None else stream
+        _check(lib().crlot_hpss_masks(self._h, C.byref(desc), spec.data_ptr(),
+                                      None if outs[0] is None else outs[0].data_ptr(),
+                                      None if outs[1] is None else outs[1].data_ptr(), S, F, ld_s, ldf_s,
+                                      lds[0][0], lds[0][1], lds[1][0], lds[1][1], s), "crlot_hpss_masks")
+        return outs[0], outs[1]
+
+    def hpss(self, x, kernel_size=31, power=2, margin=1.0, y_h=None, y_p=None, stream: int | None = None):
+        """x: (S, T) or (T,) float32 device tensor -> (y_h, y_p), each (S, F * H): the
+        harmonic and the percussive part of x (crlot_hpss; librosa.effects.hpss):
+        istft_ola of stft(x) under each of hpss_masks' masks, bit for bit, with the
+        spectra and the masks in the plan's scratch.  Pass y_h=False or y_p=False to
+        skip that part (None is returned in its place).  The plan must have no
+        stored spectral mask."""
+        if x.dim() == 1:
+            up = lambda y: y[None] if y is not None and y is not False else y  # noqa: E731
+            yh, yp = self.hpss(x[None], kernel_size, power, margin, up(y_h), up(y_p), stream)
+            return (None if yh is None else yh[0]), (None if yp is None else yp[0])
+        desc = _hpss_desc(kernel_size, power, margin)
+        if y_h is False and y_p is False:
+            raise ValueError("at least one of y_h and y_p must be computed")
+        S, T = _spectrogram_x_layout(*_tensor_layout(x))
+        if getattr(self, "_mask", None) is not None:
+            raise ValueError("hpss: the plan has a stored spectral mask; clear it first")
+        dev = self._device_index()
+        L = self.frame_count(T) * self.hop_size
+        outs, lds = [], []
+        for y in (y_h, y_p):
+            if y is False:
+                outs.append(None)
+                lds.append(0)
+                continue
+            if y is None:
+                y = _torch().empty((S, L), dtype=x.dtype, device=x.device)
+            lds.append(_gl_y_layout(*_tensor_layout(y), dev, S, L))
+            if _tensors_overlap(y, x) or any(o is not None and _tensors_overlap(y, o) for o in outs):
+                raise ValueError("an output overlaps x or the other output")
+            outs.append(y)
+        s = _stream_handle(x) if stream is None else stream
+        _check(lib().crlot_hpss(self._h, C.byref(desc), x.data_ptr(), None if outs[0] is None else outs[0].data_ptr(),
+                                None if outs[1] is None else outs[1].data_ptr(), S, T, _ld(x, 0, T), lds[0], lds[1],
+                                s), "crlot_hpss")
+        return outs[0], outs[1]
 
     def pitch_shift(self, x, resampler=None, semitones: float | None = None, max_den: int = 256, y=None,
                     stream: int | None = None):

@@ -1917,6 +1917,185 @@ int crlot_griffin_lim(crlot_plan* p, const float* d_mag, int64_t ld_mag, int64_t
 
 }  // extern "C"
 
+// ------------------------------------------------------------------ HPSS
+// crlot_hpss_masks runs the two median kernels (hpss.hip; the contract is in
+// include/crlot_dsp.h) over slices of the streams, the medians along frequency in
+// the stream's scratch slot.  crlot_hpss is, per slice, crlot_stft's dispatch, the
+// same two kernels and crlot_istft_ola's dispatch once per output, each with its
+// mask as an argument: nothing is stored in the plan.
+namespace {
+
+int hpss_desc_check(const crlot_hpss_desc* d) {
+    if (!d) return fail(CRLOT_EINVAL, "null HPSS descriptor");
+    for (const int32_t w : {d->win_harm, d->win_perc}) {
+        if (w <= 0 || !(w & 1)) return fail(CRLOT_EINVAL, "HPSS windows must be odd and positive");
+        if (w > 63) return fail(CRLOT_EUNSUPPORTED, "HPSS windows above 63 are not supported");
+    }
+    if (d->power != 1 && d->power != 2 && d->power != CRLOT_HPSS_HARD)
+        return fail(CRLOT_EUNSUPPORTED, "HPSS power must be 1, 2 or CRLOT_HPSS_HARD");
+    for (const double m : {d->margin_harm, d->margin_perc})
+        if (!(std::isfinite(m) && m >= 1.0)) return fail(CRLOT_EINVAL, "HPSS margins must be finite and >= 1");
+    return CRLOT_OK;
+}
+
+crlot::HpssArgs hpss_args(const crlot_hpss_desc& d, const float* spec, float* pbuf, float* mh, float* mp,
+                          int64_t ld_spec, int64_t ldf_spec, int64_t ld_mh, int64_t ldf_mh, int64_t ld_mp,
+                          int64_t ldf_mp, int64_t F, int32_t ns, int32_t bins) {
+    crlot::HpssArgs a{};
+    a.spec = spec;
+    a.pbuf = pbuf;
+    a.mask_h = mh;
+    a.mask_p = mp;
+    a.ld_spec = ld_spec;
+    a.ldf_spec = ldf_spec;
+    a.ld_mh = ld_mh;
+    a.ldf_mh = ldf_mh;
+    a.ld_mp = ld_mp;
+    a.ldf_mp = ldf_mp;
+    a.F = F;
+    a.n_streams = ns;
+    a.bins = bins;
+    a.win_harm = d.win_harm;
+    a.win_perc = d.win_perc;
+    a.power = d.power;
+    a.mh = float(d.margin_harm);
+    a.mp = float(d.margin_perc);
+    return a;
+}
+
+int hpss_masks_run(const crlot::HpssArgs& a, hipStream_t s) {
+    const hipError_t e = crlot::launch_hpss_masks(a, s);
+    return e == hipSuccess ? CRLOT_OK : hip_fail(e, "HPSS kernel launch");
+}
+
+}  // namespace
+
+extern "C" {
+
+int crlot_hpss_masks(crlot_plan* p, const crlot_hpss_desc* d, const float* d_spec, float* d_mask_h, float* d_mask_p,
+                     int32_t n_streams, int64_t F, int64_t ld_spec, int64_t ldf_spec, int64_t ld_mh, int64_t ldf_mh,
+                     int64_t ld_mp, int64_t ldf_mp, void* stream) {
+    // (the descriptor and the output pointers first: they need no plan)
+    if (const int rc = hpss_desc_check(d); rc != CRLOT_OK) return rc;
+    if (!d_mask_h && !d_mask_p) return fail(CRLOT_EINVAL, "both masks are null");
+    if (!p) return fail(CRLOT_EINVAL, "null plan");
+    if (n_streams < 0 || F < 0) return fail(CRLOT_EINVAL, "negative size");
+    LaunchScope ls(p, stream);
+    if (n_streams == 0 || F == 0) return CRLOT_OK;
+    if (F > INT32_MAX) return fail(CRLOT_EUNSUPPORTED, "too many frames per stream");
+    if (!d_spec) return fail(CRLOT_EINVAL, "null buffer");
+    const int64_t row = p->geo.n + 2, bins = p->geo.n / 2 + 1;
+    const bool many = n_streams > 1;
+    if (ldf_spec < row || (many && ld_spec < (F - 1) * ldf_spec + row) ||
+        (d_mask_h && (ldf_mh < bins || (many && ld_mh < (F - 1) * ldf_mh + bins))) ||
+        (d_mask_p && (ldf_mp < bins || (many && ld_mp < (F - 1) * ldf_mp + bins))))
+        return fail(CRLOT_EINVAL, "leading dimension too small");
+    if (!aligned8(d_spec) || (ldf_spec & 1) || (many && (ld_spec & 1)))
+        return fail(CRLOT_EINVAL, "spectra are complex float pairs: 8-byte aligned rows");
+    if ((d_mask_h && !aligned4(d_mask_h)) || (d_mask_p && !aligned4(d_mask_p)))
+        return fail(CRLOT_EINVAL, "mask rows must be 4-byte aligned floats");
+    if (!many) ld_spec = F * ldf_spec, ld_mh = F * ldf_mh, ld_mp = F * ldf_mp;  // (one stream: not read)
+    const int64_t spec_len = gl_extent(n_streams, F, ld_spec, ldf_spec, row);
+    const int64_t mh_len = gl_extent(n_streams, F, ld_mh, ldf_mh, bins);
+    const int64_t mp_len = gl_extent(n_streams, F, ld_mp, ldf_mp, bins);
+    if ((d_mask_h && spec_ranges_overlap(d_spec, spec_len, d_mask_h, mh_len)) ||
+        (d_mask_p && spec_ranges_overlap(d_spec, spec_len, d_mask_p, mp_len)) ||
+        (d_mask_h && d_mask_p && spec_ranges_overlap(d_mask_h, mh_len, d_mask_p, mp_len)))
+        return fail(CRLOT_EINVAL, "an output overlaps the input or the other output");
+    DeviceGuard g(p->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    std::lock_guard<std::mutex> lk(p->mu);
+    crlot::Scratch* sc = scratch_slot(p, s);
+    if (!sc) return fail(CRLOT_EHIP, "scratch slot");
+    const int64_t per_stream = F * bins * int64_t(sizeof(float));
+    const int64_t slice = std::max<int64_t>(1, std::min<int64_t>(n_streams, kFeatWorkspaceCap / per_stream));
+    if (const int rc = ensure_workspace(sc, slice * per_stream); rc != CRLOT_OK) return rc;
+    for (int64_t s0 = 0; s0 < n_streams; s0 += slice) {
+        const int32_t ns = int32_t(std::min<int64_t>(slice, n_streams - s0));
+        ls.ctl.rec = crlot::LaunchRecord{};  // (the record lists the last slice's launches)
+        const crlot::HpssArgs a =
+            hpss_args(*d, d_spec + s0 * ld_spec, sc->work, d_mask_h ? d_mask_h + s0 * ld_mh : nullptr,
+                      d_mask_p ? d_mask_p + s0 * ld_mp : nullptr, ld_spec, ldf_spec, ld_mh, ldf_mh, ld_mp, ldf_mp, F,
+                      ns, int32_t(bins));
+        if (const int rc = hpss_masks_run(a, s); rc != CRLOT_OK) return rc;
+    }
+    return CRLOT_OK;
+}
+
+int crlot_hpss(crlot_plan* p, const crlot_hpss_desc* d, const float* d_x, float* d_y_h, float* d_y_p,
+               int32_t n_streams, int64_t T, int64_t ld_x, int64_t ld_y_h, int64_t ld_y_p, void* stream) {
+    if (const int rc = hpss_desc_check(d); rc != CRLOT_OK) return rc;
+    if (!d_y_h && !d_y_p) return fail(CRLOT_EINVAL, "both outputs are null");
+    if (!p) return fail(CRLOT_EINVAL, "null plan");
+    if (n_streams < 0 || T < 0) return fail(CRLOT_EINVAL, "negative size");
+    LaunchScope ls(p, stream);
+    const int64_t F = frames_for(p, T);
+    if (n_streams == 0 || F == 0) return CRLOT_OK;
+    if (F > INT32_MAX) return fail(CRLOT_EUNSUPPORTED, "too many frames per stream");
+    if (!d_x) return fail(CRLOT_EINVAL, "null buffer");
+    const int64_t n = p->geo.n, row = n + 2, bins = n / 2 + 1, L = F * p->geo.h;
+    const bool many = n_streams > 1;
+    if (ld_x < T || (many && ((d_y_h && ld_y_h < L) || (d_y_p && ld_y_p < L))))
+        return fail(CRLOT_EINVAL, "leading dimension too small");
+    if (!many) ld_y_h = ld_y_p = L;  // (one stream: not read)
+    const int64_t x_len = (n_streams - 1) * ld_x + T;
+    const int64_t yh_len = (n_streams - 1) * ld_y_h + L, yp_len = (n_streams - 1) * ld_y_p + L;
+    if ((d_y_h && spec_ranges_overlap(d_x, x_len, d_y_h, yh_len)) ||
+        (d_y_p && spec_ranges_overlap(d_x, x_len, d_y_p, yp_len)) ||
+        (d_y_h && d_y_p && spec_ranges_overlap(d_y_h, yh_len, d_y_p, yp_len)))
+        return fail(CRLOT_EINVAL, "an output overlaps the input or the other output");
+    DeviceGuard g(p->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    std::lock_guard<std::mutex> lk(p->mu);
+    if (p->mask.p)
+        return fail(CRLOT_EINVAL, "HPSS: the plan has a stored mask; the separation masks are the spectral step");
+    crlot::Scratch* sc = scratch_slot(p, s);
+    if (!sc) return fail(CRLOT_EHIP, "scratch slot");
+    // Per stream: the spectra (flat rows of N+2 floats), the medians along frequency,
+    // one mask per output, and what the staged routes of the two halves add, one
+    // after the other in the same floats.  A route follows the plan, the extents and
+    // the rows' alignment, which every slice shares.
+    const crlot::DevTables t = tables(p);
+    const bool in_staged = stft_route(p, t, d_x, T, ld_x, n_streams, F).kind == RouteKind::kStaged;
+    const bool out_staged = (d_y_h && istft_route(p, t, d_y_h, F, ld_y_h, n_streams).kind == RouteKind::kStaged) ||
+                            (d_y_p && istft_route(p, t, d_y_p, F, ld_y_p, n_streams).kind == RouteKind::kStaged);
+    const int64_t stage = std::max<int64_t>(in_staged ? F * n : 0, out_staged ? F * (row + n) : 0);
+    const int64_t n_masks = (d_y_h ? 1 : 0) + (d_y_p ? 1 : 0);
+    const int64_t per_stream = (F * row + (1 + n_masks) * F * bins + stage) * int64_t(sizeof(float));
+    const int64_t slice = std::max<int64_t>(1, std::min<int64_t>(n_streams, kFeatWorkspaceCap / per_stream));
+    if (const int rc = ensure_workspace(sc, slice * per_stream); rc != CRLOT_OK) return rc;
+    float* spec = sc->work;
+    float* pbuf = spec + slice * F * row;
+    float* mask_h = d_y_h ? pbuf + slice * F * bins : nullptr;
+    float* mask_p = d_y_p ? pbuf + (d_y_h ? 2 : 1) * slice * F * bins : nullptr;
+    float* work = pbuf + (1 + n_masks) * slice * F * bins;
+    for (int64_t s0 = 0; s0 < n_streams; s0 += slice) {
+        const int32_t ns = int32_t(std::min<int64_t>(slice, n_streams - s0));
+        ls.ctl.rec = crlot::LaunchRecord{};  // (the record lists the last slice's launches)
+        int rc = stft_impl(p, d_x + s0 * ld_x, spec, ns, T, ld_x, F, F * row, row, in_staged ? work : nullptr, s);
+        if (rc != CRLOT_OK) return rc;
+        const crlot::HpssArgs a = hpss_args(*d, spec, pbuf, mask_h, mask_p, F * row, row, F * bins, bins, F * bins,
+                                            bins, F, ns, int32_t(bins));
+        rc = hpss_masks_run(a, s);
+        if (rc != CRLOT_OK) return rc;
+        for (int o = 0; o < 2; ++o) {
+            float* y = o == 0 ? d_y_h : d_y_p;
+            if (!y) continue;
+            const int64_t ld_y = o == 0 ? ld_y_h : ld_y_p;
+            crlot::SpecMask mask;
+            mask.p = o == 0 ? mask_h : mask_p;
+            mask.ld_frame = bins;
+            mask.ld_stream = F * bins;
+            rc = istft_impl(p, spec, y + s0 * ld_y, ns, F, F * row, row, ld_y, out_staged ? work : nullptr,
+                            out_staged ? work + int64_t(ns) * F * row : nullptr, s, &mask);
+            if (rc != CRLOT_OK) return rc;
+        }
+    }
+    return CRLOT_OK;
+}
+
+}  // extern "C"
+
 // ------------------------------------------------------------------ FFT plans
 // A real plan of nfft points owns an STFT plan of frame nfft; a complex plan of
 // nfft points owns one of frame 2*nfft, whose pass twiddles are those of an

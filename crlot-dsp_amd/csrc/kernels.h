@@ -592,6 +592,25 @@ bool gl_iter_supported(int n, int h, bool momentum);
 hipError_t launch_gl_iter(const Geometry& g, const DevTables& t, const GlIterArgs& a, int n_streams, int64_t F,
                           hipStream_t s);
 
+// ---- hpss.hip: harmonic / percussive masks (crlot_hpss_masks / crlot_hpss; the contract is in include/crlot_dsp.h)
+// spec rows of `bins` float pairs (even leading dimensions, 8-byte aligned), mask rows
+// of `bins` floats (either mask nullable), pbuf: n_streams F bins floats that receive
+// the medians along frequency.  K_hpss_freq, then K_hpss_time (chunks recorded; the
+// plan's chunk knob applies).
+struct HpssArgs {
+    const float* spec;
+    float* pbuf;
+    float* mask_h;
+    float* mask_p;
+    int64_t ld_spec, ldf_spec, ld_mh, ldf_mh, ld_mp, ldf_mp;
+    int64_t F;
+    int32_t n_streams, bins;
+    int32_t win_harm, win_perc;  // odd, 1 .. 63
+    int32_t power;               // 1, 2 or CRLOT_HPSS_HARD
+    float mh, mp;                // (float)margin
+};
+hipError_t launch_hpss_masks(const HpssArgs& a, hipStream_t s);
+
 // dsp::FrameQueue frames on the device: [stream][F][N] from x [stream][ld_x]
 hipError_t launch_fq_frames(const float* x, int64_t T, int64_t ld_x, int n_streams, float* frames, int64_t F,
                             int64_t N, int64_t H, int64_t pad, int pad_mode, hipStream_t s);

@@ -181,6 +181,8 @@ extern "C" const char* crlot_kernel_name(int32_t id) {
         case CRLOT_K_RESAMPLE_ANY: return "k_resample_any";
         case CRLOT_K_GL_PROJECT: return "k_gl_project";
         case CRLOT_K_GL_ITER: return "k_gl_iter";
+        case CRLOT_K_HPSS_FREQ: return "k_hpss_freq";
+        case CRLOT_K_HPSS_TIME: return "k_hpss_time";
         case CRLOT_K_EXPERIMENT: return "k_experiment";
         default: return "unknown";
     }

@@ -237,6 +237,9 @@ int crlot_test_inject(int32_t what, int32_t count);
 #define CRLOT_K_RESAMPLE_ANY 38  /* crlot_resample: one lane per output, any filter length */
 #define CRLOT_K_GL_PROJECT 39   /* crlot_gl_project: the Griffin-Lim projection over spectra in HBM */
 #define CRLOT_K_GL_ITER 40      /* crlot_griffin_lim: one fused iteration y_i -> y_i+1 (N = 256 / 512 / 1024) */
+/* (41 is not assigned: crlot_kernel_name(41) stays "unknown") */
+#define CRLOT_K_HPSS_FREQ 42    /* crlot_hpss_masks: the running median along frequency */
+#define CRLOT_K_HPSS_TIME 43    /* crlot_hpss_masks: the running median along time, then the masks */
 #define CRLOT_K_EXPERIMENT 99    /* experiment builds only */
 typedef struct crlot_launch_info {
     int32_t n_kernels;
@@ -736,6 +739,79 @@ int crlot_gl_project(crlot_plan* plan, const float* d_spec, const float* d_tprev
 int crlot_griffin_lim(crlot_plan* plan, const float* d_mag, int64_t ld_mag, int64_t ld_frame_mag,
                       const float* d_init, int64_t ld_init, int64_t ld_frame_init, float* d_y, int64_t ld_y,
                       int32_t n_streams, int64_t F, int32_t n_iter, double momentum, void* stream);
+
+/* ---------------------------------------------------------------- HPSS
+ * Harmonic / percussive source separation (librosa.decompose.hpss,
+ * librosa.effects.hpss): two median filters over the magnitudes of spectra in
+ * crlot_stft's layout (bin b of frame k of stream s at
+ * d_spec[s*ld_spec + k*ld_frame + 2*b], bins = N/2+1), and from them two soft
+ * masks in the layout crlot_plan_set_spectral_mask reads.
+ *
+ * Every step is one correctly rounded float32 operation, no FMA.
+ *  1. Magnitude.  re and im are sanitized on load as IFftPlan's sanitize does
+ *     (NaN / Inf -> 0, |v| < 1e-30 -> 0); the imaginary parts of bins 0 and N/2 are
+ *     taken as 0;  m = sqrtf(fl(fl(re*re) + fl(im*im)))  (CRLOT_FEAT_MAGNITUDE).
+ *     Domain: components in {0} or [2^-60, 2^60] in size; beyond it the formula is
+ *     still evaluated literally.
+ *  2. Medians.  With r = (w-1)/2 and ext(i, n) = (j = i mod 2n, 0 <= j < 2n;
+ *     j < n ? j : 2n-1-j):
+ *       h[k][b] = median of m[ext(k+d, F)][b],    d = -r_h .. r_h   (along time, win_harm)
+ *       p[k][b] = median of m[k][ext(b+d, bins)], d = -r_p .. r_p   (along frequency, win_perc)
+ *     which is scipy.ndimage.median_filter(mode='reflect'), also where the window is
+ *     longer than the axis.  Windows are odd, 1 <= w <= 63 (even or non-positive:
+ *     CRLOT_EINVAL; above 63: CRLOT_EUNSUPPORTED).  A median is a selection: its
+ *     bits do not depend on how it is found.
+ *  3. Masks.  margin_harm, margin_perc: finite doubles >= 1 (else CRLOT_EINVAL), cast
+ *     once to float (mh, mp).  power is 1, 2 or CRLOT_HPSS_HARD (anything else:
+ *     CRLOT_EUNSUPPORTED; powf has no bit contract).  Harmonic mask: X = h,
+ *     R = fl(p*mh); percussive mask: X = p, R = fl(h*mp);
+ *       Z = max(X, R)
+ *       Z < FLT_MIN:  mask = (mh == 1 && mp == 1) ? 0.5f : 0      (librosa's split_zeros)
+ *       else  a = X / Z, b = R / Z;  power 2: a = fl(a*a), b = fl(b*b);  mask = a / fl(a + b)
+ *     CRLOT_HPSS_HARD (librosa's power = inf):  mask = X > R ? 1 : 0; a tie gives 0
+ *     in both masks.
+ *  4. Output.  d_mask_h[s*ld_mask_h + k*ld_frame_mask_h + b], likewise d_mask_p;
+ *     ld_frame >= N/2+1; the floats between N/2+1 and ld_frame are not written.
+ *
+ * crlot_hpss_masks: either mask pointer may be NULL (both: CRLOT_EINVAL).  Spectra:
+ * ld_frame >= N+2, even leading dimensions, an 8-byte aligned base; masks: 4-byte
+ * aligned; with n_streams > 1 every stream stride covers its F rows; with
+ * n_streams == 1 the stream strides are not read.  Any overlap of an output with
+ * the input or with the other output is CRLOT_EINVAL.  F = 0 or n_streams = 0:
+ * CRLOT_OK, nothing written.  64-bit addressing.  Kernels: CRLOT_K_HPSS_FREQ (p
+ * into the stream's scratch slot, F * bins floats per stream, the streams in
+ * slices under 256 MiB or one stream's worth), then CRLOT_K_HPSS_TIME (h and both
+ * masks), which crlot_plan_set_chunks splits along time; the bits do not depend
+ * on the split, the batch or the leading dimensions.
+ *
+ * crlot_hpss is by definition the composition S = crlot_stft(x); (Mh, Mp) =
+ * crlot_hpss_masks(S); y_h = crlot_istft_ola(S) with Mh as the plan's spectral
+ * mask; y_p likewise with Mp; F * H samples per stream and output.  It equals
+ * that composition bit for bit under the plan's own pairing setting and
+ * spectral gain (the gain rides as in crlot_istft_ola).  Either output may be
+ * NULL (both: CRLOT_EINVAL); its mask and its inversion are then skipped.  A plan
+ * with a stored mask is CRLOT_EINVAL; the call stores nothing in the plan (the
+ * inversions take their mask as an argument), so host threads may run it on one
+ * plan on different HIP streams.  Overlaps among x, y_h and y_p: CRLOT_EINVAL.
+ * Workspace (the stream's scratch slot): the spectra, p, one mask per output and
+ * the staged routes' frames; the streams go in slices under the 256 MiB cap of
+ * crlot_griffin_lim, or one stream's worth if that is more.  The bits never
+ * depend on slicing, chunking, the batch size, a stream's position in the batch
+ * or the leading dimensions.  crlot_plan_last_launch lists the last slice's
+ * kernels.  With n_streams == 1, ld_y_h and ld_y_p are not read. */
+#define CRLOT_HPSS_HARD (-1) /* crlot_hpss_desc.power: the hard masks (power = inf) */
+typedef struct crlot_hpss_desc {
+    int32_t win_harm, win_perc; /* median windows along time / frequency: odd, 1 .. 63 (librosa: 31) */
+    int32_t power;              /* 1, 2 or CRLOT_HPSS_HARD */
+    int32_t reserved;           /* 0 */
+    double margin_harm, margin_perc; /* finite, >= 1 */
+} crlot_hpss_desc;
+int crlot_hpss_masks(crlot_plan* plan, const crlot_hpss_desc* desc, const float* d_spec, float* d_mask_h,
+                     float* d_mask_p, int32_t n_streams, int64_t F, int64_t ld_spec, int64_t ld_frame_spec,
+                     int64_t ld_mask_h, int64_t ld_frame_mask_h, int64_t ld_mask_p, int64_t ld_frame_mask_p,
+                     void* stream);
+int crlot_hpss(crlot_plan* plan, const crlot_hpss_desc* desc, const float* d_x, float* d_y_h, float* d_y_p,
+               int32_t n_streams, int64_t T, int64_t ld_x, int64_t ld_y_h, int64_t ld_y_p, void* stream);
 
 /* host helpers (no device) */
 #define CRLOT_MEL_HTK 0

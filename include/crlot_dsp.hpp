@@ -281,6 +281,24 @@ class StftEngine {
                                 n_iter, momentum, s),
               "crlot_griffin_lim");
     }
+    // The harmonic / percussive soft masks of spectra in stft_device's layout (crlot_hpss_masks): either mask
+    // may be null; mask rows of bins() floats, the layout set_spectral_mask takes.  Dense layouts when the
+    // leading dimensions are 0: rows of 2 * bins() floats (bins() for the masks), F rows per stream.
+    void hpss_masks_device(const crlot_hpss_desc& desc, const float* d_spec, float* d_mask_h, float* d_mask_p,
+                           int n_streams, int64_t F, int64_t ld_spec = 0, int64_t ld_frame = 0, int64_t ld_mask = 0,
+                           int64_t ld_frame_mask = 0, hipStream_t s = nullptr) {
+        const int64_t lf = ld_frame ? ld_frame : 2 * int64_t(bins()), ls = ld_spec ? ld_spec : F * lf;
+        const int64_t lfm = ld_frame_mask ? ld_frame_mask : bins(), lm = ld_mask ? ld_mask : F * lfm;
+        check(crlot_hpss_masks(plan_.get(), &desc, d_spec, d_mask_h, d_mask_p, n_streams, F, ls, lf, lm, lfm, lm, lfm,
+                               s),
+              "crlot_hpss_masks");
+    }
+    // x -> its harmonic and percussive parts (crlot_hpss): d_y_h, d_y_p [n_streams][ld_y], frame_count(T) * hop
+    // samples each; either may be null.  The plan must have no stored spectral mask.
+    void hpss_device(const crlot_hpss_desc& desc, const float* d_x, float* d_y_h, float* d_y_p, int n_streams,
+                     int64_t T, int64_t ld_x, int64_t ld_y, hipStream_t s = nullptr) {
+        check(crlot_hpss(plan_.get(), &desc, d_x, d_y_h, d_y_p, n_streams, T, ld_x, ld_y, ld_y, s), "crlot_hpss");
+    }
     // per-frame real mask rows of bins(): frame k of stream s at d_mask + s*ld_stream + k*ld_frame
     // (ld_stream 0: one mask shared by the streams); nullptr clears it
     void set_spectral_mask(const float* d_mask_or_null, int64_t ld_frame = 0, int64_t ld_stream = 0) {
