@@ -216,7 +216,8 @@ __global__ __launch_bounds__(64 * kSW, 3) void k_pair_feat(const PairFeatArgs pa
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     const int m = 4 * m4 + u;
-                    v[m] = dev::pc_mk(xin[m] * wv[u], xin[m + SH] * wv[u]);
+                    // (no frame k + 1: zeros, not the samples after the last frame; as k_pair_stft)
+                    v[m] = dev::pc_mk(xin[m] * wv[u], (two ? xin[m + SH] : 0.0f) * wv[u]);
                 }
             }
             dev::pair_fft_fwd(v, buf, tw, tw, lane);

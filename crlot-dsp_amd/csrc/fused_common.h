@@ -212,6 +212,11 @@ __device__ __forceinline__ bool pair_code_paired(uint32_t code, bool has_b) {
 // one all-zero INPUT frame -- exact silence next to an onset -- is transformed
 // frame by frame, so the silent frame's spectrum is exact zeros instead of
 // ~eps |mate's spectrum|, which a mask that attenuates the mate would not shrink.
+// The last frame of an odd frame count has no mate: the forward kernels whose output
+// is a spectrum (K_pair_stft's families, K_pair_feat) put zeros in the imaginary
+// half, as the inverse loads zeros for a row past F -- not the samples after the
+// frame, which belong to no frame (DROP framing keeps up to a hop of them) and
+// would leave ~eps |those samples| in the last frame's spectrum.
 // any_nonzero: this lane holds a value that is not +-0 among f[0 .. n) (the bit
 // patterns ORed, one v_or3 per two values; NaN counts as non-zero).
 // hop_live: 1 when any sample of the hop (SH per lane, whole wave) is non-zero;

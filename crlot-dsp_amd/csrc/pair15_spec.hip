@@ -337,6 +337,10 @@ __global__ __launch_bounds__(64 * kQW, 2) void k_p15_stft(const PairSpecArgs pa)
         const bool two = k + 1 < w.f1;
         float* ra = so + int64_t(k) * pa.ld_frame;
         float* rb = ra + pa.ld_frame;
+        if (!two) {  // (no frame k + 1: zeros, not the samples after the last frame; fused_common.h)
+#pragma unroll
+            for (int m = 0; m < E; ++m) fb[m] = 0.0f;
+        }
         const bool paired = q15_ok(fa, xlo, xhi) && q15_ok(fb, xlo, xhi) && (!two || q15_no_lone_silent<L>(fa, fb));
         dev::pc v[16];
         if (paired) {

@@ -119,7 +119,8 @@ __global__ __launch_bounds__(64 * kSW, 3) void k_pair_stft(const PairSpecArgs pa
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     const int m = 4 * m4 + u;
-                    v[m] = dev::pc_mk(xin[m] * wv[u], xin[m + SH] * wv[u]);
+                    // (no frame k + 1: zeros, not the samples after the last frame; fused_common.h)
+                    v[m] = dev::pc_mk(xin[m] * wv[u], (two ? xin[m + SH] : 0.0f) * wv[u]);
                 }
             }
             dev::pair_fft_fwd(v, buf, tw, tw, lane);
@@ -440,7 +441,8 @@ __global__ __launch_bounds__(64 * kSW) void k_pair512_stft(const PairSpecArgs pa
         // (a lone all-zero frame of the pair is transformed alone: exact zeros; fused_common.h)
         if ((hopok & kPairHops) == kPairHops && pair_code_paired(hops_live_code<NB>(hoplive), two)) {
 #pragma unroll
-            for (int m = 0; m < E; ++m) v[m] = dev::pc_mk(xin[m] * wa[m], xin[m + SH] * wa[m]);
+            for (int m = 0; m < E; ++m)  // (no frame k + 1: zeros, not the samples after the last frame)
+                v[m] = dev::pc_mk(xin[m] * wa[m], (two ? xin[m + SH] : 0.0f) * wa[m]);
             dev::wave_lds_fence();
             dev::pair512_fwd(v, buf, tw, lane);
             dev::pc zp[5];

@@ -345,8 +345,8 @@ __global__ __launch_bounds__(G::L, 2) void k_pairwg_stft(const PairSpecArgs pa) 
             constexpr int P = decltype(pc_)::value;
             dev::pc v[E];
 #pragma unroll
-            for (int m = 0; m < E; ++m)
-                v[m] = paired ? dev::pc_mk(xin[m] * wa[m], xin[m + SH] * wa[m])
+            for (int m = 0; m < E; ++m)  // (no frame k + 1: zeros, not the samples after the last frame)
+                v[m] = paired ? dev::pc_mk(xin[m] * wa[m], (two ? xin[m + SH] : 0.0f) * wa[m])
                               : dev::pc_mk(dev::sanit(xin[m + P * SH] * wa[m]), 0.0f);
             tw.fwd(v, sm.xb, sm.tb, t);
 #pragma unroll

@@ -257,9 +257,9 @@ __global__ __launch_bounds__(QN<K>::THREADS, 2) void k_pn_stft(const PairSpecArg
         auto pass = [&](auto pc_) {  // P = 0 / 1: frame k / k+1 alone; paired: both (P = 0)
             constexpr int P = decltype(pc_)::value;
 #pragma unroll
-            for (int m = 0; m < E; ++m)
+            for (int m = 0; m < E; ++m)  // (no frame k + 1: zeros, not the samples after the last frame; fused_common.h)
                 if (G::valid(m, t))
-                    sm.buf[t + G::L * m] = paired ? dev::pc_mk(fa[m] * wa[m], fb[m] * wa[m])
+                    sm.buf[t + G::L * m] = paired ? dev::pc_mk(fa[m] * wa[m], (two ? fb[m] : 0.0f) * wa[m])
                                                 : dev::pc_mk(dev::sanit((P ? fb[m] : fa[m]) * wa[m]), 0.0f);
             dev::pn_fence<K>();
             G::fwd(sm.buf, sm.tw, t);
