@@ -115,6 +115,17 @@ class HpssDesc(C.Structure):
                 ("margin_harm", C.c_double), ("margin_perc", C.c_double)]
 
 
+class ConvolverDesc(C.Structure):
+    """crlot_convolver_desc (include/crlot_dsp.h)."""
+    _fields_ = [("block", C.c_int32), ("n_filters", C.c_int32), ("device", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ConvolverLaunch(C.Structure):
+    """crlot_convolver_launch (include/crlot_dsp.h): a convolver's last delay-line launch."""
+    _fields_ = [("kernel", C.c_int32), ("threads", C.c_int32), ("grid", C.c_int64), ("n_chunks", C.c_int32),
+                ("chunk", C.c_int32), ("tile", C.c_int32), ("reserved", C.c_int32)]
+
+
 class FftDesc(C.Structure):
     """crlot_fft_desc (include/crlot_dsp.h)."""
     _fields_ = [("domain", C.c_int32), ("nfft", C.c_int32), ("device", C.c_int32)]
@@ -181,6 +192,17 @@ def lib():
         "crlot_griffin_lim": ([vp, vp, i64, i64, vp, i64, i64, vp, i64, i32, i64, i32, C.c_double, vp], C.c_int),
         "crlot_hpss_masks": ([vp, C.POINTER(HpssDesc), vp, vp, vp, i32, i64, i64, i64, i64, i64, i64, i64, vp], C.c_int),
         "crlot_hpss": ([vp, C.POINTER(HpssDesc), vp, vp, vp, i32, i64, i64, i64, i64, vp], C.c_int),
+        "crlot_convolver_create": ([C.POINTER(ConvolverDesc), fp, i64, i64, C.POINTER(vp)], C.c_int),
+        "crlot_convolver_destroy": ([vp], None),
+        "crlot_convolver_info": ([vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i64), C.POINTER(i32)], C.c_int),
+        "crlot_convolver_prepare": ([vp], C.c_int),
+        "crlot_convolver_spectra": ([vp, fp], C.c_int),
+        "crlot_convolver_plan": ([vp], vp),
+        "crlot_convolve_output_length": ([vp, i64], i64),
+        "crlot_convolver_set_chunks": ([vp, i32], C.c_int),
+        "crlot_convolver_last_launch": ([vp, C.POINTER(ConvolverLaunch)], C.c_int),
+        "crlot_fdl_mac": ([vp, vp, vp, i32, i64, i64, i64, i64, i64, i64, vp], C.c_int),
+        "crlot_convolve": ([vp, vp, vp, i32, i64, i64, i64, vp], C.c_int),
         "crlot_resample_geometry": ([C.POINTER(ResamplerDesc), C.POINTER(ResamplerGeometry)], C.c_int),
         "crlot_resample_table_host": ([C.POINTER(ResamplerDesc), fp], C.c_int),
         "crlot_rational_approx": ([C.c_double, i32, C.POINTER(i32), C.POINTER(i32)], C.c_int),
@@ -1337,6 +1359,184 @@ class Resampler:
         s = _stream_handle(x) if stream is None else stream
         _check(lib().crlot_resample(self._h, x.data_ptr(), y.data_ptr(), S, T, _ld(x, 0, T), ld_y, s),
                "crlot_resample")
+        return y
+
+
+# ----------------------------------------------------------------- partitioned FFT convolution
+def _convolve_layouts(x_layout, y_layout, device: int, K: int):
+    """Validate Convolver.convolve's tensors from their plain descriptions (shape,
+    strides in elements, dtype name, device index or None for a host tensor; y_layout
+    None: the call allocates y): x (S, T) float32 and y (S, >= T + K - 1) float32 on
+    `device`, rows contiguous and not overlapping.  Returns (S, T, L, ld_x, ld_y)."""
+    S, T = _spectrogram_x_layout(*x_layout)
+    if int(x_layout[3]) != int(device):
+        raise ValueError(f"x must live on the convolver's device {device}, not {x_layout[3]}")
+    L = 0 if T == 0 else T + int(K) - 1
+    ld_x = int(x_layout[1][0]) if S > 1 else max(T, 1)
+    if S > 1 and ld_x < T:
+        raise ValueError("x rows overlap: the stream stride is below T")
+    ld_y = max(L, 1) if y_layout is None else _gl_y_layout(*y_layout, device, S, L)
+    return S, T, L, ld_x, ld_y
+
+
+def _fdl_layouts(spec_layout, out_layout, device: int, bins: int, P: int, F_out=None):
+    """The same for Convolver.fdl_mac: spec (S, F_in, bins) complex64 and out
+    (S, F_out, bins) complex64 on `device` (_stretch_spec_layout's rules); F_out
+    defaults to F_in + P - 1.  Returns (S, F_in, F_out, ld_in, ldf_in, ld_out, ldf_out),
+    the last two None when the call allocates out."""
+    ld_in, ldf_in = _stretch_spec_layout(*spec_layout, device, bins)
+    S, F_in = int(spec_layout[0][0]), int(spec_layout[0][1])
+    if F_out is None:
+        F_out = F_in + int(P) - 1 if F_in > 0 else 0
+    if isinstance(F_out, bool) or int(F_out) != F_out or int(F_out) < 0:
+        raise ValueError("F_out must be a non-negative integer")
+    F_out = int(F_out)
+    if out_layout is None:
+        return S, F_in, F_out, ld_in, ldf_in, None, None
+    ld_out, ldf_out = _stretch_spec_layout(*out_layout, device, bins, "out", (S, F_out, bins))
+    return S, F_in, F_out, ld_in, ldf_in, ld_out, ldf_out
+
+
+class _BorrowedPlan(Plan):
+    """A Plan over a handle another object owns (Convolver.plan): closing it forgets
+    the handle and destroys nothing; it keeps its owner alive."""
+
+    def __init__(self, handle, owner, cfg: PlanConfig):
+        self.cfg, self._h, self._owner = cfg, handle, owner
+        self._mask, self._mask_extent = None, None
+        n, hop, ring = C.c_int32(), C.c_int32(), C.c_int32()
+        _check(lib().crlot_plan_info(self._h, C.byref(n), C.byref(hop), C.byref(ring)))
+        self.frame_size, self.hop_size, self.ring_len = n.value, hop.value, ring.value
+
+    def close(self):
+        self._h, self._owner = None, None
+
+
+class Convolver:
+    """Full linear convolution of every stream with a long FIR as uniformly
+    partitioned overlap-add (crlot_convolver_create / crlot_convolve; the numbers of
+    torchaudio.functional.fftconvolve).  h: (K,) or (n_filters, K) float32 taps on
+    the host, stream s uses filter s mod n_filters; block: the partition size B (the
+    engine plan has N = 2B, H = B).  Creation touches no device: the plan and the
+    filter spectra are made by prepare(), .plan or the first device call."""
+
+    def __init__(self, h, block: int = 512, device: int | None = None):
+        self._h, self._plan = None, None
+        taps = np.ascontiguousarray(np.asarray(h.cpu() if hasattr(h, "cpu") else h), np.float32)
+        if taps.ndim == 1:
+            taps = taps[None]
+        if taps.ndim != 2 or taps.shape[1] < 1:
+            raise ValueError("h must be (K,) or (n_filters, K) with K >= 1")
+        self._device = None if device is None else int(device)
+        d = ConvolverDesc(int(block), int(taps.shape[0]), -1 if device is None else int(device), 0)
+        hd = C.c_void_p()
+        _check(lib().crlot_convolver_create(C.byref(d), _fptr(taps), taps.shape[1], taps.shape[1], C.byref(hd)),
+               "crlot_convolver_create")
+        self._h = hd
+        b, nf, k, p = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int32()
+        _check(lib().crlot_convolver_info(self._h, C.byref(b), C.byref(nf), C.byref(k), C.byref(p)),
+               "crlot_convolver_info")
+        self.block, self.n_filters, self.taps, self.partitions = b.value, nf.value, k.value, p.value
+        self.frame_size, self.bins = 2 * b.value, b.value + 1
+
+    def close(self):
+        if getattr(self, "_plan", None) is not None:
+            self._plan.close()
+            self._plan = None
+        if getattr(self, "_h", None):
+            lib().crlot_convolver_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # interpreter shutdown
+            pass
+
+    @property
+    def device(self) -> int:
+        """The device index (device=None: the current device at the first use)."""
+        if self._device is None:
+            self._device = int(_torch().cuda.current_device())
+        return self._device
+
+    def prepare(self):
+        """Create the engine plan, upload and transform the filter now."""
+        dev = self.device
+        with _torch().cuda.device(dev):
+            _check(lib().crlot_convolver_prepare(self._h), "crlot_convolver_prepare")
+
+    @property
+    def plan(self) -> Plan:
+        """The engine plan (N = 2B, H = B, ZERO_PAD, a window of B ones and B zeros,
+        unit norm), borrowed: use its stft / istft_ola / set_frame_pairing /
+        set_chunks / last_launch; do not replace its tables, gain or mask."""
+        if self._plan is None:
+            self.prepare()
+            h = lib().crlot_convolver_plan(self._h)
+            if not h:
+                _check(EHIP, "crlot_convolver_plan")
+            cfg = PlanConfig(frame_size=self.frame_size, hop_size=self.block, window_type=RECT,
+                             boundary_mode=ZERO_PAD, analysis_window=True, apply_window_inside=False,
+                             device=self.device)
+            self._plan = _BorrowedPlan(C.c_void_p(h), self, cfg)
+        return self._plan
+
+    def output_length(self, T: int) -> int:
+        return _check(int(lib().crlot_convolve_output_length(self._h, int(T))), "crlot_convolve_output_length")
+
+    def spectra(self) -> np.ndarray:
+        """The filter spectra H, (n_filters, P, N/2+1) complex64, from the device."""
+        self.prepare()
+        out = np.zeros((self.n_filters, self.partitions, 2 * self.bins), np.float32)
+        _check(lib().crlot_convolver_spectra(self._h, _fptr(out)), "crlot_convolver_spectra")
+        return out.view(np.complex64)
+
+    def set_chunks(self, n: int = 0):
+        """Force the delay line to split every stream's output frames into min(n, F_out)
+        chunks (0: the library's choice).  Output bits never depend on it."""
+        _check(lib().crlot_convolver_set_chunks(self._h, int(n)), "crlot_convolver_set_chunks")
+
+    def last_launch(self) -> dict:
+        r = ConvolverLaunch()
+        _check(lib().crlot_convolver_last_launch(self._h, C.byref(r)), "crlot_convolver_last_launch")
+        d = {k: getattr(r, k) for k, _ in ConvolverLaunch._fields_ if k != "reserved"}
+        d["name"] = kernel_name(r.kernel) if r.kernel else None
+        return d
+
+    def fdl_mac(self, spec, out=None, F_out: int | None = None, stream: int | None = None):
+        """spec: (S, F_in, N/2+1) or (F_in, N/2+1) complex64 device tensor -> out:
+        (S, F_out, N/2+1), F_out = F_in + P - 1 by default: per bin the complex FIR of
+        the filter's partition spectra along the frame axis (crlot_fdl_mac)."""
+        if len(spec.shape) == 2:
+            return self.fdl_mac(spec[None], None if out is None else out[None], F_out, stream)[0]
+        S, F_in, F_out, ld_in, ldf_in, ld_out, ldf_out = _fdl_layouts(
+            _tensor_layout(spec), None if out is None else _tensor_layout(out), self.device, self.bins,
+            self.partitions, F_out)
+        if out is None:
+            out = _torch().empty((S, F_out, self.bins), dtype=spec.dtype, device=spec.device)
+            ld_out, ldf_out = 2 * F_out * self.bins, 2 * self.bins
+        elif _tensors_overlap(spec, out):
+            raise ValueError("out overlaps spec")
+        s = _stream_handle(spec) if stream is None else stream
+        _check(lib().crlot_fdl_mac(self._h, spec.data_ptr(), out.data_ptr(), S, F_in, F_out, ld_in, ldf_in, ld_out,
+                                   ldf_out, s), "crlot_fdl_mac")
+        return out
+
+    def convolve(self, x, y=None, stream: int | None = None):
+        """x: (S, T) or (T,) float32 device tensor -> y: (S, T + K - 1), the full
+        convolution of stream s with filter s mod n_filters (crlot_convolve).  A wider
+        y keeps its samples from T + K - 1 on."""
+        if x.dim() == 1:
+            return self.convolve(x[None], None if y is None else y[None], stream)[0]
+        S, T, L, ld_x, ld_y = _convolve_layouts(_tensor_layout(x), None if y is None else _tensor_layout(y),
+                                                self.device, self.taps)
+        if y is None:
+            y = _torch().empty((S, L), dtype=x.dtype, device=x.device)
+        elif _tensors_overlap(x, y):
+            raise ValueError("y overlaps x")
+        s = _stream_handle(x) if stream is None else stream
+        _check(lib().crlot_convolve(self._h, x.data_ptr(), y.data_ptr(), S, T, ld_x, ld_y, s), "crlot_convolve")
         return y
 
 

@@ -2096,6 +2096,83 @@ int crlot_hpss(crlot_plan* p, const crlot_hpss_desc* d, const float* d_x, float*
 
 }  // extern "C"
 
+// ------------------------------------------------------------------ partitioned FFT convolution
+// crlot_convolve is, per slice of streams, crlot_stft's dispatch on the convolver's
+// engine plan, the delay line (convolve.hip, through convolve_host.cpp) and
+// crlot_istft_ola's dispatch.  The inverse writes F_out B samples per stream: when
+// that is more than the T + K - 1 the caller's rows receive, it writes dense rows in
+// the workspace and a strided copy crops them into y.
+extern "C" int crlot_convolve(crlot_convolver* c, const float* d_x, float* d_y, int32_t n_streams, int64_t T,
+                              int64_t ld_x, int64_t ld_y, void* stream) {
+    if (!c) return fail(CRLOT_EINVAL, "null convolver");
+    if (n_streams < 0 || T < 0) return fail(CRLOT_EINVAL, "negative size");
+    if (T > (int64_t(1) << 48)) return fail(CRLOT_EINVAL, "T must lie in [0, 2^48]");
+    if (n_streams == 0 || T == 0) return CRLOT_OK;
+    if (!d_x || !d_y) return fail(CRLOT_EINVAL, "null buffer");
+    crlot::ConvolverShape cs{};
+    if (const int rc = crlot::convolver_ready(c, cs); rc != CRLOT_OK) return rc;
+    crlot_plan* p = cs.plan;
+    const int64_t B = cs.B, L = T + cs.K - 1;
+    const int64_t F = (T + B - 1) / B, Fo = (L + B - 1) / B;
+    if (Fo > INT32_MAX) return fail(CRLOT_EUNSUPPORTED, "too many frames per stream");
+    const bool many = n_streams > 1;
+    if (ld_x < T || (many && ld_y < L)) return fail(CRLOT_EINVAL, "leading dimension too small");
+    if (!many) ld_y = L;  // (one stream: not read)
+    if (spec_ranges_overlap(d_x, (n_streams - 1) * ld_x + T, d_y, (n_streams - 1) * ld_y + L))
+        return fail(CRLOT_EINVAL, "the input and output overlap");
+    LaunchScope ls(p, stream);
+    DeviceGuard g(p->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    std::lock_guard<std::mutex> lk(p->mu);
+    if (frames_for(p, T) != F || p->mask.p || p->has_gain)
+        return fail(CRLOT_EINVAL, "the convolver's plan was reconfigured (framing, gain or mask)");
+    crlot::Scratch* sc = scratch_slot(p, s);
+    if (!sc) return fail(CRLOT_EHIP, "scratch slot");
+    // Per stream: both spectra (flat rows of N+2 floats), the uncropped output when the
+    // caller's rows are shorter than it, and what the staged routes of the two halves
+    // add, one after the other in the same floats.  A route follows the plan, the
+    // extents and the rows' alignment, which every slice shares.
+    const crlot::DevTables t = tables(p);
+    const int64_t n = p->geo.n, row = n + 2, Lo = Fo * B;
+    const bool crop = L != Lo;
+    // (z: the workspace is 256-byte aligned and z starts a multiple of 64 floats into
+    // it; a route reads the pointer's alignment alone)
+    float* const y_route = crop ? reinterpret_cast<float*>(uintptr_t(256)) : d_y;
+    const int64_t ld_z = crop ? Lo : ld_y;
+    const bool in_staged = stft_route(p, t, d_x, T, ld_x, n_streams, F).kind == RouteKind::kStaged;
+    const bool out_staged = istft_route(p, t, y_route, Fo, ld_z, n_streams).kind == RouteKind::kStaged;
+    const int64_t stage = std::max<int64_t>(in_staged ? F * n : 0, out_staged ? Fo * (row + n) : 0);
+    const int64_t per_stream = ((F + Fo) * row + stage + (crop ? Lo : 0)) * int64_t(sizeof(float));
+    const int64_t slice = std::max<int64_t>(1, std::min<int64_t>(n_streams, kFeatWorkspaceCap / per_stream));
+    const int64_t z_at = (slice * ((F + Fo) * row + stage) + 63) / 64 * 64;
+    if (const int rc = ensure_workspace(sc, (z_at + (crop ? slice * Lo : 0)) * int64_t(sizeof(float))); rc != CRLOT_OK)
+        return rc;
+    float* spec_in = sc->work;
+    float* spec_out = spec_in + slice * F * row;
+    float* work = spec_out + slice * Fo * row;
+    float* z = sc->work + z_at;
+    for (int64_t s0 = 0; s0 < n_streams; s0 += slice) {
+        const int32_t ns = int32_t(std::min<int64_t>(slice, n_streams - s0));
+        ls.ctl.rec = crlot::LaunchRecord{};  // (the record lists the last slice's launches)
+        int rc = stft_impl(p, d_x + s0 * ld_x, spec_in, ns, T, ld_x, F, F * row, row, in_staged ? work : nullptr, s);
+        if (rc != CRLOT_OK) return rc;
+        // (the filter of stream s0 + i is (s0 + i) mod n_filters: a slice starts where the delay line is told)
+        rc = crlot::fdl_mac_run(c, spec_in, spec_out, ns, F, Fo, F * row, row, Fo * row, row, s, int32_t(s0));
+        if (rc != CRLOT_OK) return rc;
+        float* y_slice = crop ? z : d_y + s0 * ld_y;
+        rc = istft_impl(p, spec_out, y_slice, ns, Fo, Fo * row, row, ld_z, out_staged ? work : nullptr,
+                        out_staged ? work + int64_t(ns) * Fo * row : nullptr, s);
+        if (rc != CRLOT_OK) return rc;
+        if (crop) {
+            const hipError_t e =
+                hipMemcpy2DAsync(d_y + s0 * ld_y, size_t(ld_y) * sizeof(float), z, size_t(Lo) * sizeof(float),
+                                 size_t(L) * sizeof(float), size_t(ns), hipMemcpyDeviceToDevice, s);
+            if (e != hipSuccess) return hip_fail(e, "convolve output crop");
+        }
+    }
+    return CRLOT_OK;
+}
+
 // ------------------------------------------------------------------ FFT plans
 // A real plan of nfft points owns an STFT plan of frame nfft; a complex plan of
 // nfft points owns one of frame 2*nfft, whose pass twiddles are those of an

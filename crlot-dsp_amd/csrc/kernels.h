@@ -611,6 +611,40 @@ struct HpssArgs {
 };
 hipError_t launch_hpss_masks(const HpssArgs& a, hipStream_t s);
 
+// ---- convolve.hip: the frequency-domain delay line (crlot_fdl_mac / crlot_convolve; the contract is in include/crlot_dsp.h)
+// in / out: spectra rows of `bins` float pairs (even leading dimensions, 8-byte
+// aligned); h: the filter spectra [n_filters][P][2 * ldh2] floats, rows of ldh2 float
+// pairs.  Stream s of the call reads filter (first_stream + s) mod n_filters.
+struct FdlArgs {
+    const float* in;
+    float* out;
+    const float* h;
+    int64_t ld_in, ldf_in, ld_out, ldf_out;
+    int64_t F_in, F_out;
+    int32_t n_streams, bins;
+    int32_t P, n_filters;
+    int32_t ldh2;
+    int32_t first_stream;
+};
+// chunks: output-frame chunks per stream forced on the walk (0: the launcher's
+// choice).  Fills *rec with what it launched.  hipErrorInvalidValue: a bad
+// argument or a grid beyond 2^31-1.
+hipError_t launch_fdl_mac(const FdlArgs& a, int chunks, crlot_convolver_launch* rec, hipStream_t s);
+// convolve_host.cpp, for crlot_convolve (abi.cpp).  convolver_ready: the engine plan
+// exists and the filter spectra are on the device (takes the object's lock);
+// fdl_mac_run: crlot_fdl_mac's body for a caller that has checked the arguments
+// (takes the object's lock); first_stream: the batch position of the call's first
+// stream (a slice of crlot_convolve), which selects its filter
+struct ConvolverShape {
+    int32_t B, P, device;
+    int64_t K;
+    crlot_plan* plan;
+};
+int convolver_ready(crlot_convolver* c, ConvolverShape& out);
+int fdl_mac_run(crlot_convolver* c, const float* d_in, float* d_out, int32_t n_streams, int64_t F_in, int64_t F_out,
+                int64_t ld_in, int64_t ldf_in, int64_t ld_out, int64_t ldf_out, hipStream_t s,
+                int32_t first_stream = 0);
+
 // dsp::FrameQueue frames on the device: [stream][F][N] from x [stream][ld_x]
 hipError_t launch_fq_frames(const float* x, int64_t T, int64_t ld_x, int n_streams, float* frames, int64_t F,
                             int64_t N, int64_t H, int64_t pad, int pad_mode, hipStream_t s);

@@ -240,6 +240,8 @@ int crlot_test_inject(int32_t what, int32_t count);
 /* (41 is not assigned: crlot_kernel_name(41) stays "unknown") */
 #define CRLOT_K_HPSS_FREQ 42    /* crlot_hpss_masks: the running median along frequency */
 #define CRLOT_K_HPSS_TIME 43    /* crlot_hpss_masks: the running median along time, then the masks */
+/* (44 is not assigned: crlot_kernel_name(44) stays "unknown") */
+#define CRLOT_K_FDL_MAC 45      /* crlot_fdl_mac: the frequency-domain delay line of crlot_convolve */
 #define CRLOT_K_EXPERIMENT 99    /* experiment builds only */
 typedef struct crlot_launch_info {
     int32_t n_kernels;
@@ -812,6 +814,98 @@ int crlot_hpss_masks(crlot_plan* plan, const crlot_hpss_desc* desc, const float*
                      void* stream);
 int crlot_hpss(crlot_plan* plan, const crlot_hpss_desc* desc, const float* d_x, float* d_y_h, float* d_y_p,
                int32_t n_streams, int64_t T, int64_t ld_x, int64_t ld_y_h, int64_t ld_y_p, void* stream);
+
+/* ---------------------------------------------------------------- partitioned FFT convolution
+ * Full linear convolution of every stream with a long FIR (a room response, a
+ * cabinet or HRTF filter, a matched filter, a linear-phase EQ), as uniformly
+ * partitioned overlap-add (torchaudio.functional.fftconvolve /
+ * scipy.signal.oaconvolve give the same numbers): y[s][n] = sum_k h[q][k] x[s][n-k]
+ * for n < T + K - 1, q = s mod n_filters.
+ *
+ * The object.  A crlot_convolver holds n_filters filters of K taps (K in
+ * [1, 2^20], n_filters in [1, 65536]; host rows ld_h >= K floats apart; every tap
+ * finite), cut into P = ceil(K / B) partitions of B = `block` taps, and its own
+ * crlot_plan, the engine plan: N = 2B, H = B, CRLOT_ZERO_PAD, analysis_window = 1,
+ * apply_window_inside = 0, ola_gain = 1, the window table replaced by B ones then B
+ * zeros, the norm table by ones, no gain, no mask.  With it crlot_stft gives the
+ * spectrum of every zero-padded input block (F = ceil(T / B) frames) and
+ * crlot_istft_ola overlap-adds 2B-sample results.  B must make N = 2B a frame size
+ * crlot_plan_create accepts (else CRLOT_EINVAL; power-of-two B in 128..2048 are
+ * tested).  crlot_convolver_create touches no device: the plan is created and the
+ * filter uploaded and transformed by crlot_convolver_prepare, crlot_convolver_plan
+ * or the first device call.  The filter spectra are H[q][p][.] = crlot_rfft_batched
+ * of block p of filter q zero-padded to N: the per-frame (kiss_fftr split)
+ * transform whatever the plan's pairing setting, computed once, so toggling
+ * pairing on the borrowed plan never changes H.  crlot_convolver_spectra copies
+ * them to the host, [n_filters][P][N+2] floats.  crlot_convolver_plan lends the
+ * engine plan (NULL on failure, crlot_last_error says why): do not destroy it, do
+ * not replace its tables, gain or mask.  The object has its own lock; several host
+ * threads may share it.
+ *
+ * crlot_fdl_mac: the frequency-domain delay line, a complex FIR along the frame
+ * axis per bin.  Spectra in crlot_stft's layout on both sides (frame k of stream s
+ * at d[s*ld + k*ldf + 2*b]; 8-byte aligned, even leading dimensions, ldf >= N+2).
+ * Values.  For stream s, output frame f < F_out, bin b <= N/2, q = s mod n_filters:
+ *   re = im = +0;
+ *   for j = max(0, f-P+1) .. min(f, F_in-1), ascending, with p = f - j,
+ *       (Hr, Hi) = H[q][p][b], (Xr, Xi) = X[s][j][b], in this order:
+ *     re = fmaf(Hr, Xr, re);  re = fmaf(-Hi, Xi, re);
+ *     im = fmaf(Hr, Xi, im);  im = fmaf(Hi, Xr, im);
+ *   out[s][f][b] = (re + 0.0f, im + 0.0f).
+ * Rows outside [0, F_in) are not loaded; an empty range stores +0.  X is taken as
+ * it is (no sanitizing: crlot_stft's forward already mapped NaN / Inf to 0).
+ * Invariance.  Every output is an independent chain in a fixed order, so its bits
+ * do not depend on the frame chunking, the register tile, the batch, a stream's
+ * position, the leading dimensions or the slice of crlot_convolve.  (Ascending j
+ * is the order in which a sliding or per-hop implementation meets the inputs.)
+ * d_spec_out must not overlap d_spec_in (CRLOT_EINVAL).  F_in >= 0, F_out >= 0;
+ * F_out = 0 or n_streams = 0: CRLOT_OK, nothing written.  Only the N/2+1 bins of
+ * each output row are written.  Kernel: CRLOT_K_FDL_MAC, one wave per 64 adjacent
+ * bins of one stream and chunk of output frames; crlot_convolver_set_chunks forces
+ * min(n, F_out) chunks per stream (0: the library's choice; a test knob),
+ * crlot_convolver_last_launch reports the object's last launch on any stream.
+ *
+ * crlot_convolve is by definition, on the engine plan, crlot_stft(x) (F_in =
+ * ceil(T / B) frames) -> crlot_fdl_mac to F_out = ceil((T + K - 1) / B) frames ->
+ * crlot_istft_ola, cropped to crlot_convolve_output_length(T) = T + K - 1 samples
+ * per stream (0 for T = 0), bit for bit under the engine plan's pairing and chunk
+ * settings.  ld_x >= T; ld_y >= T + K - 1 when n_streams > 1 (it may be below
+ * F_out B: nothing is written past sample T + K - 2 of a row).  x and y must not
+ * overlap.  T = 0 or n_streams = 0: CRLOT_OK, nothing written.  Both spectra (and,
+ * unless T + K - 1 is a multiple of B, the uncropped output) live in the stream's
+ * scratch slot of the engine plan; streams go in slices so that this workspace
+ * stays within 256 MiB, or one stream's worth if that is more.
+ * crlot_plan_last_launch on the engine plan lists the last slice's kernels. */
+typedef struct crlot_convolver crlot_convolver;
+typedef struct crlot_convolver_desc {
+    int32_t block;      /* B: N = 2B must be a frame size the plan accepts */
+    int32_t n_filters;  /* >= 1; stream s uses filter s mod n_filters */
+    int32_t device;     /* -1 = current */
+    int32_t reserved;   /* 0 */
+} crlot_convolver_desc;
+typedef struct crlot_convolver_launch {
+    int32_t kernel;     /* CRLOT_K_FDL_MAC; 0: no launch yet */
+    int32_t threads;    /* per workgroup */
+    int64_t grid;       /* workgroups */
+    int32_t n_chunks;   /* chunks of output frames per stream */
+    int32_t chunk;      /* output frames per chunk */
+    int32_t tile;       /* output frames per register tile */
+    int32_t reserved;
+} crlot_convolver_launch;
+int crlot_convolver_create(const crlot_convolver_desc* desc, const float* h /* host [n_filters][ld_h] */, int64_t K,
+                           int64_t ld_h, crlot_convolver** out);
+void crlot_convolver_destroy(crlot_convolver* c);
+int crlot_convolver_info(const crlot_convolver* c, int32_t* block, int32_t* n_filters, int64_t* K, int32_t* P);
+int crlot_convolver_prepare(crlot_convolver* c);
+int crlot_convolver_spectra(crlot_convolver* c, float* host_out /* [n_filters][P][N+2] */);
+crlot_plan* crlot_convolver_plan(crlot_convolver* c);
+int64_t crlot_convolve_output_length(const crlot_convolver* c, int64_t T);
+int crlot_convolver_set_chunks(crlot_convolver* c, int32_t chunks_per_stream);
+int crlot_convolver_last_launch(const crlot_convolver* c, crlot_convolver_launch* out);
+int crlot_fdl_mac(crlot_convolver* c, const float* d_spec_in, float* d_spec_out, int32_t n_streams, int64_t F_in,
+                  int64_t F_out, int64_t ld_in, int64_t ldf_in, int64_t ld_out, int64_t ldf_out, void* stream);
+int crlot_convolve(crlot_convolver* c, const float* d_x, float* d_y, int32_t n_streams, int64_t T, int64_t ld_x,
+                   int64_t ld_y, void* stream);
 
 /* host helpers (no device) */
 #define CRLOT_MEL_HTK 0

@@ -171,6 +171,80 @@ class Resampler {
     crlot_resampler* r_ = nullptr;
 };
 
+// Full linear convolution of every stream with a long FIR as uniformly partitioned
+// overlap-add (crlot_convolver_*): h holds n_filters rows of K taps, stream s uses
+// filter s mod n_filters, block is the partition size B.  Owns its engine plan.
+class Convolver {
+   public:
+    Convolver(const float* h, int64_t K, int block = 512, int n_filters = 1, int64_t ld_h = 0, int device = -1) {
+        crlot_convolver_desc d{};
+        d.block = block;
+        d.n_filters = n_filters;
+        d.device = device;
+        check(crlot_convolver_create(&d, h, K, ld_h > 0 ? ld_h : K, &c_), "crlot_convolver_create");
+    }
+    explicit Convolver(const std::vector<float>& h, int block = 512, int device = -1)
+        : Convolver(h.data(), int64_t(h.size()), block, 1, 0, device) {}
+    ~Convolver() { crlot_convolver_destroy(c_); }
+    Convolver(const Convolver&) = delete;
+    Convolver& operator=(const Convolver&) = delete;
+    Convolver(Convolver&& o) noexcept : c_(o.c_) { o.c_ = nullptr; }
+    Convolver& operator=(Convolver&& o) noexcept {
+        if (this != &o) {
+            crlot_convolver_destroy(c_);
+            c_ = o.c_;
+            o.c_ = nullptr;
+        }
+        return *this;
+    }
+    int block() const { return info_i32(0); }
+    int n_filters() const { return info_i32(1); }
+    int partitions() const { return info_i32(2); }
+    int64_t taps() const {
+        int64_t k = 0;
+        check(crlot_convolver_info(c_, nullptr, nullptr, &k, nullptr), "crlot_convolver_info");
+        return k;
+    }
+    void prepare() { check(crlot_convolver_prepare(c_), "crlot_convolver_prepare"); }
+    // the engine plan, borrowed (N = 2 block, H = block): never destroy it
+    crlot_plan* plan() {
+        crlot_plan* p = crlot_convolver_plan(c_);
+        check(p ? 0 : CRLOT_EHIP, "crlot_convolver_plan");
+        return p;
+    }
+    int64_t output_length(int64_t T) const {
+        const int64_t L = crlot_convolve_output_length(c_, T);
+        check(L < 0 ? int(L) : 0, "crlot_convolve_output_length");
+        return L;
+    }
+    // the filter spectra, [n_filters][P][N+2] floats
+    std::vector<float> spectra() {
+        std::vector<float> h(size_t(n_filters()) * partitions() * (2 * size_t(block()) + 2));
+        check(crlot_convolver_spectra(c_, h.data()), "crlot_convolver_spectra");
+        return h;
+    }
+    // d_x [n_streams][ld_x], T samples each -> d_y [n_streams][ld_y], output_length(T) each; no overlap
+    void convolve_device(const float* d_x, float* d_y, int n_streams, int64_t T, int64_t ld_x, int64_t ld_y,
+                         hipStream_t s = nullptr) {
+        check(crlot_convolve(c_, d_x, d_y, n_streams, T, ld_x, ld_y, s), "crlot_convolve");
+    }
+    // the delay line alone: spectra in crlot_stft's layout, F_in frames in, F_out frames out; no overlap
+    void fdl_mac_device(const float* d_spec_in, float* d_spec_out, int n_streams, int64_t F_in, int64_t F_out,
+                        int64_t ld_in, int64_t ldf_in, int64_t ld_out, int64_t ldf_out, hipStream_t s = nullptr) {
+        check(crlot_fdl_mac(c_, d_spec_in, d_spec_out, n_streams, F_in, F_out, ld_in, ldf_in, ld_out, ldf_out, s),
+              "crlot_fdl_mac");
+    }
+    crlot_convolver* get() const { return c_; }
+
+   private:
+    int info_i32(int which) const {
+        int32_t v[3] = {0, 0, 0};
+        check(crlot_convolver_info(c_, &v[0], &v[1], nullptr, &v[2]), "crlot_convolver_info");
+        return v[which];
+    }
+    crlot_convolver* c_ = nullptr;
+};
+
 // Batched round trip: n_streams mono streams, each T samples.
 class StftEngine {
    public:
