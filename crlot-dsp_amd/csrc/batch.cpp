@@ -13,17 +13,10 @@
 #include "ab.h"
 #include "call.h"
 #include "kernels.h"
-
-namespace crlot {
-int set_error(int code, const std::string& msg);  // abi.cpp
-}
+#include "plan_internal.h"
 
 namespace crlot {
 namespace {
-
-int hip_fail(hipError_t e, const char* what) {
-    return set_error(CRLOT_EHIP, std::string(what) + ": " + hipGetErrorString(e));
-}
 
 std::atomic<int> g_mode{2};
 constexpr float kOne = 1.0f;

@@ -1,5 +1,5 @@
 // batch.h -- batched speculation of the reference's per-frame drop-in loop
-// (internal; batch.cpp, hooks in abi.cpp fft_host and objects.cpp).
+// (internal; batch.cpp, hooks in fft_host.cpp fft_host and objects.cpp).
 //
 // bench/e2e_benchmark.cc:138-186 runs, per frame k of a signal pushed whole
 // into a Framer:  pop -> p = frame * w -> IFftPlan::forward(p) -> inverse ->
@@ -168,7 +168,7 @@ struct BatchSpec {
 // position, no wrap); *first = the first frame whose unread contributions remain
 bool ola_can_continue(const crlot_ola* o, const BatchSpec* b);
 
-// abi.cpp fft_host, under sh->mu: a contiguous batch-1 real forward / inverse.
+// fft_host.cpp fft_host, under sh->mu: a contiguous batch-1 real forward / inverse.
 // 1: served into `out`; 0: not (take the ordinary path); < 0: error.
 int batch_forward(SharedServer* sh, crlot_plan* inner, int64_t n, const float* in, float* out);
 // inner: the FFT plan (null: serve only, never learn a spectral gain -- the
@@ -185,7 +185,7 @@ int ola_materialize_locked(crlot_ola* o);
 int batch_attach(SharedServer* sh, crlot_ola* o, int64_t j0, int64_t R, const float* d_ws, const float* d_den,
                  float gain, hipStream_t tables_stream, uint64_t tgen);
 int batch_wait_y(BatchSpec* b);
-// abi.cpp: the plan's K_rfft + K_irfft in one launch (CRLOT_EUNSUPPORTED: none)
+// fft_host.cpp: the plan's K_rfft + K_irfft in one launch (CRLOT_EUNSUPPORTED: none)
 int plan_rfft_irfft(crlot_plan* p, const float* in, float* spec, float* r, float* r_host, int32_t batch,
                     void* stream);
 // the attached object's ring once every batch frame j0 .. M-1 was pushed with no

@@ -14,6 +14,7 @@
 // system-scope loads read either).
 #include "call.h"
 #include "ab.h"
+#include "plan_internal.h"
 
 #include <immintrin.h>
 
@@ -27,19 +28,16 @@
 #include <vector>
 
 namespace crlot {
-int set_error(int code, const std::string& msg);  // abi.cpp
 
 namespace {
-int fail(int code, const std::string& msg) { return set_error(code, msg); }
-int hip_fail(hipError_t e, const char* what) { return fail(CRLOT_EHIP, std::string(what) + ": " + hipGetErrorString(e)); }
-
-struct DeviceGuard {
+// (restores the device found at entry whatever the calls in between left current)
+struct CurrentDeviceGuard {
     int prev = -1;
-    explicit DeviceGuard(int dev) {
+    explicit CurrentDeviceGuard(int dev) {
         if (hipGetDevice(&prev) != hipSuccess) prev = -1;
         if (dev >= 0 && dev != prev) (void)hipSetDevice(dev);
     }
-    ~DeviceGuard() {
+    ~CurrentDeviceGuard() {
         int cur = -1;
         if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
     }
@@ -64,7 +62,7 @@ constexpr size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 CallServer::~CallServer() { release(); }
 
 void CallServer::release() {
-    DeviceGuard g(device_);
+    CurrentDeviceGuard g(device_);
     (void)stop();
     if (dblk_) (void)hipFree(dblk_);
     if (dhost_) (void)hipHostFree(dhost_);
@@ -86,7 +84,7 @@ int CallServer::create(int device, int e, int depth, size_t in_cap, size_t out_c
     sv->device_ = device;
     sv->e_ = e;
     sv->depth_ = depth;
-    DeviceGuard g(device);
+    CurrentDeviceGuard g(device);
     hipError_t err;
     if ((err = hipStreamCreateWithFlags(&sv->s_, hipStreamNonBlocking)) ||
         (err = hipEventCreateWithFlags(&sv->ev_, hipEventDisableTiming))) {
@@ -157,7 +155,7 @@ int CallServer::alloc(size_t in_cap, size_t out_cap, size_t spec_cap) {
 
 int CallServer::grow(size_t in_cap, size_t out_cap, size_t spec_cap) {
     if (in_cap <= in_cap_ && out_cap <= out_cap_ && spec_cap <= spec_cap_) return CRLOT_OK;
-    DeviceGuard g(device_);
+    CurrentDeviceGuard g(device_);
     int rc = drain();
     if (rc == CRLOT_OK) rc = stop();
     if (rc != CRLOT_OK) return rc;
@@ -469,7 +467,7 @@ SharedServer* shared_server_any(int device, int P, int* rc) {
     if (!s) {
         static const bool hooked = [] { return std::atexit(stop_shared_servers) == 0; }();
         (void)hooked;
-        DeviceGuard g(device);
+        CurrentDeviceGuard g(device);
         SharedServer* n = new SharedServer();
         n->e = -P;
         n->any_waves = waves;
@@ -515,7 +513,7 @@ SharedServer* shared_server(int device, int e, int* rc) {
     if (!s) {
         static const bool hooked = [] { return std::atexit(stop_shared_servers) == 0; }();
         (void)hooked;
-        DeviceGuard g(device);
+        CurrentDeviceGuard g(device);
         SharedServer* n = new SharedServer();
         n->e = e;
         const int P = 64 * e;

@@ -1,23 +1,13 @@
 // convolve_host.cpp -- the host side of partitioned FFT convolution (include/crlot_dsp.h,
 // "partitioned FFT convolution"): descriptor and filter checks, the object with its
-// engine plan and filter spectra, crlot_fdl_mac.  The kernel and its tile policy
-// are in convolve.hip; crlot_convolve is beside crlot_hpss in abi.cpp, where the
-// spectral entries' dispatch and the scratch slots live.
-#include <hip/hip_runtime.h>
+// engine plan and filter spectra, crlot_fdl_mac and crlot_convolve.  The kernel and
+// its tile policy are in convolve.hip.
 
-#include <algorithm>
 #include <cmath>
-#include <cstdint>
-#include <mutex>
-#include <string>
-#include <vector>
 
-#include "crlot_dsp.h"
-#include "kernels.h"
+#include "plan_internal.h"
 
-namespace crlot {
-int set_error(int code, const std::string& msg);  // abi.cpp: crlot_last_error()'s slot
-}
+using namespace crlot;
 
 struct crlot_convolver {
     crlot_convolver_desc desc{};
@@ -34,25 +24,8 @@ struct crlot_convolver {
 
 namespace {
 
-int fail(int code, const std::string& msg) { return crlot::set_error(code, msg); }
-int hip_fail(hipError_t e, const char* what) {
-    return fail(CRLOT_EHIP, std::string(what) + ": " + hipGetErrorString(e));
-}
-
 constexpr int64_t kMaxTaps = int64_t(1) << 20;
 constexpr int32_t kMaxFilters = 65536;
-
-struct DeviceGuard {
-    int prev = -1;
-    bool moved = false;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (dev >= 0 && dev != prev) moved = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceGuard() {
-        if (moved && prev >= 0) (void)hipSetDevice(prev);
-    }
-};
 
 // N = 2B as crlot_plan_create judges a frame size: even, powers of two 256 .. 4096 or
 // a size of the mixed-radix path up to 16384
@@ -60,16 +33,6 @@ bool frame_size_ok(int64_t n) {
     if (n < 2 || n > 16384) return false;
     const bool pow2 = (n & (n - 1)) == 0;
     return (pow2 && n >= 256 && n <= 4096) || crlot::any_supported(int(n / 2));
-}
-
-bool ranges_overlap(const float* a, int64_t a_len, const float* b, int64_t b_len) {
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return a0 < b0 + uintptr_t(b_len) * sizeof(float) && b0 < a0 + uintptr_t(a_len) * sizeof(float);
-}
-
-// floats from the first to one past the last element of spectra rows
-int64_t spec_extent(int32_t n_streams, int64_t F, int64_t ld, int64_t ldf, int64_t row) {
-    return (n_streams - 1) * ld + (F - 1) * ldf + row;
 }
 
 // The engine plan and the filter spectra, made once (caller holds c->mu).  The
@@ -156,25 +119,12 @@ int fdl_mac_run(crlot_convolver* c, const float* d_in, float* d_out, int32_t n_s
     const int rc = ensure_ready(c);
     if (rc != CRLOT_OK) return rc;
     DeviceGuard g(c->device);
-    FdlArgs a{};
-    a.in = d_in;
-    a.out = d_out;
-    a.h = c->d_h;
-    a.ld_in = ld_in;
-    a.ldf_in = ldf_in;
-    a.ld_out = ld_out;
-    a.ldf_out = ldf_out;
-    a.F_in = F_in;
-    a.F_out = F_out;
-    a.n_streams = n_streams;
-    a.bins = c->B + 1;
-    a.P = c->P;
-    a.n_filters = c->desc.n_filters;
-    a.ldh2 = c->B + 1;
-    a.first_stream = first_stream % c->desc.n_filters;
+    const FdlArgs a{d_in, d_out, c->d_h, ld_in, ldf_in, ld_out, ldf_out, F_in, F_out, n_streams,
+                    /*bins*/ c->B + 1, c->P, c->desc.n_filters, /*ldh2*/ c->B + 1,
+                    first_stream % c->desc.n_filters};
     const hipError_t e = launch_fdl_mac(a, c->chunks, &c->last, s);
     if (e == hipErrorInvalidValue) return fail(CRLOT_EUNSUPPORTED, "too many waves for one call");
-    return e == hipSuccess ? CRLOT_OK : hip_fail(e, "delay line kernel launch");
+    return launched(e, "delay line kernel launch");
 }
 
 }  // namespace crlot
@@ -242,7 +192,7 @@ int crlot_convolver_spectra(crlot_convolver* c, float* host_out) {
     DeviceGuard g(c->device);
     const size_t bytes = size_t(c->desc.n_filters) * c->P * (2 * size_t(c->B) + 2) * sizeof(float);
     const hipError_t e = hipMemcpy(host_out, c->d_h, bytes, hipMemcpyDeviceToHost);
-    return e == hipSuccess ? CRLOT_OK : hip_fail(e, "filter spectra download");
+    return launched(e, "filter spectra download");
 }
 
 crlot_plan* crlot_convolver_plan(crlot_convolver* c) {
@@ -284,19 +234,80 @@ int crlot_fdl_mac(crlot_convolver* c, const float* d_spec_in, float* d_spec_out,
     if ((!d_spec_in && F_in > 0) || !d_spec_out) return fail(CRLOT_EINVAL, "null buffer");
     const int64_t row = 2 * int64_t(c->B) + 2;
     const bool many = n_streams > 1;
-    if (ldf_out < row || (many && ld_out < (F_out - 1) * ldf_out + row) ||
-        (F_in > 0 && (ldf_in < row || (many && ld_in < (F_in - 1) * ldf_in + row))))
+    const Rows out{d_spec_out, ld_out, ldf_out, row};
+    if (!fits(out, n_streams, F_out) || (F_in > 0 && !fits(Rows{d_spec_in, ld_in, ldf_in, row}, n_streams, F_in)))
         return fail(CRLOT_EINVAL, "leading dimension too small");
     if (F_in == 0) d_spec_in = d_spec_out, ldf_in = row, ld_in = row;  // (never read)
-    if ((reinterpret_cast<uintptr_t>(d_spec_in) & 7u) || (reinterpret_cast<uintptr_t>(d_spec_out) & 7u) ||
-        (ldf_in & 1) || (ldf_out & 1) || (many && ((ld_in & 1) || (ld_out & 1))))
+    const Rows in{d_spec_in, ld_in, ldf_in, row};
+    if (!complex_ok(in, n_streams) || !complex_ok(out, n_streams))
         return fail(CRLOT_EINVAL, "spectra are complex float pairs: 8-byte aligned rows");
-    if (!many) ld_in = std::max<int64_t>(F_in, 1) * ldf_in, ld_out = F_out * ldf_out;  // (one stream: not read)
-    if (F_in > 0 && ranges_overlap(d_spec_in, spec_extent(n_streams, F_in, ld_in, ldf_in, row), d_spec_out,
-                                   spec_extent(n_streams, F_out, ld_out, ldf_out, row)))
+    if (F_in > 0 && overlap(d_spec_in, extent(in, n_streams, F_in), d_spec_out, extent(out, n_streams, F_out)))
         return fail(CRLOT_EINVAL, "the output spectra overlap the input spectra");
+    if (!many) ld_in = std::max<int64_t>(F_in, 1) * ldf_in, ld_out = F_out * ldf_out;  // (one stream: not read)
     return crlot::fdl_mac_run(c, d_spec_in, d_spec_out, n_streams, F_in, F_out, ld_in, ldf_in, ld_out, ldf_out,
                               static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"
+
+// crlot_convolve is, per slice of streams, crlot_stft's dispatch on the convolver's
+// engine plan, the delay line and crlot_istft_ola's dispatch.  The inverse writes
+// F_out B samples per stream: when that is more than the T + K - 1 the caller's rows
+// receive, it writes dense rows in the workspace and a strided copy crops them into y.
+extern "C" int crlot_convolve(crlot_convolver* c, const float* d_x, float* d_y, int32_t n_streams, int64_t T,
+                              int64_t ld_x, int64_t ld_y, void* stream) {
+    if (!c) return fail(CRLOT_EINVAL, "null convolver");
+    if (n_streams < 0 || T < 0) return fail(CRLOT_EINVAL, "negative size");
+    if (T > (int64_t(1) << 48)) return fail(CRLOT_EINVAL, "T must lie in [0, 2^48]");
+    if (n_streams == 0 || T == 0) return CRLOT_OK;
+    if (!d_x || !d_y) return fail(CRLOT_EINVAL, "null buffer");
+    crlot::ConvolverShape cs{};
+    if (const int rc = crlot::convolver_ready(c, cs); rc != CRLOT_OK) return rc;
+    crlot_plan* p = cs.plan;
+    const int64_t B = cs.B, L = T + cs.K - 1;
+    const int64_t F = (T + B - 1) / B, Fo = (L + B - 1) / B;
+    if (Fo > INT32_MAX) return fail(CRLOT_EUNSUPPORTED, "too many frames per stream");
+    const bool many = n_streams > 1;
+    if (ld_x < T || (many && ld_y < L)) return fail(CRLOT_EINVAL, "leading dimension too small");
+    if (!many) ld_y = L;  // (one stream: not read)
+    if (overlap(d_x, (n_streams - 1) * ld_x + T, d_y, (n_streams - 1) * ld_y + L))
+        return fail(CRLOT_EINVAL, "the input and output overlap");
+    LaunchScope ls(p, stream);
+    DeviceGuard g(p->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    std::lock_guard<std::mutex> lk(p->mu);
+    if (frames_for(p, T) != F || p->mask.p || p->has_gain)
+        return fail(CRLOT_EINVAL, "the convolver's plan was reconfigured (framing, gain or mask)");
+    // Per stream: both spectra (flat rows of N+2 floats); as the tail z, the uncropped
+    // output when the caller's rows are shorter than it
+    const int64_t row = p->geo.n + 2, Lo = Fo * B;
+    const bool crop = L != Lo;
+    const int64_t ld_z = crop ? Lo : ld_y;
+    SpecSlices sl(p, ls, s, n_streams);
+    sl.input(d_x, T, ld_x, F);
+    sl.output(crop ? workspace_row_probe() : d_y, ld_z, Fo);
+    const int r_in = sl.region(F * row), r_out = sl.region(Fo * row);
+    sl.size(crop ? Lo : 0);
+    if (const int rc = sl.reserve(); rc != CRLOT_OK) return rc;
+    float* spec_in = sl.at(r_in);
+    float* spec_out = sl.at(r_out);
+    float* z = sl.tail;
+    while (sl.next()) {
+        const int64_t s0 = sl.s0;
+        const int32_t ns = sl.ns;
+        int rc = sl.stft(d_x + s0 * ld_x, spec_in);
+        if (rc != CRLOT_OK) return rc;
+        // (the filter of stream s0 + i is (s0 + i) mod n_filters: a slice starts where the delay line is told)
+        rc = crlot::fdl_mac_run(c, spec_in, spec_out, ns, F, Fo, F * row, row, Fo * row, row, s, int32_t(s0));
+        if (rc != CRLOT_OK) return rc;
+        float* y_slice = crop ? z : d_y + s0 * ld_y;
+        if ((rc = sl.istft(spec_out, y_slice, ld_z, Fo)) != CRLOT_OK) return rc;
+        if (crop) {
+            const hipError_t e =
+                hipMemcpy2DAsync(d_y + s0 * ld_y, size_t(ld_y) * sizeof(float), z, size_t(Lo) * sizeof(float),
+                                 size_t(L) * sizeof(float), size_t(ns), hipMemcpyDeviceToDevice, s);
+            if (e != hipSuccess) return hip_fail(e, "convolve output crop");
+        }
+    }
+    return CRLOT_OK;
+}

@@ -33,31 +33,11 @@
 #include "respool.h"
 #include "crlot_dsp.h"
 #include "kernels.h"
+#include "plan_internal.h"
 
-namespace crlot {
-int set_error(int code, const std::string& msg);  // abi.cpp: crlot_last_error()'s slot
-}
-
-namespace {
-
-int fail(int code, const std::string& msg) { return crlot::set_error(code, msg); }
-int hip_fail(hipError_t e, const char* what) {
-    return fail(CRLOT_EHIP, std::string(what) + ": " + hipGetErrorString(e));
-}
-
-struct DeviceGuard {
-    int prev = -1;
-    bool moved = false;  // (restore only what this guard changed: one runtime query per call)
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (dev >= 0 && dev != prev) moved = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceGuard() {
-        if (moved && prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
-}  // namespace
+using crlot::DeviceGuard;
+using crlot::fail;
+using crlot::hip_fail;
 
 // =================================================================== Framer
 struct crlot_framer {

@@ -2,23 +2,14 @@
 // pitch shift"): descriptor checks, the table builder, crlot_rational_approx, the
 // output length, the object with its device table, and the entries.  The kernels
 // and their tile policy are in resample.hip; crlot_pitch_shift is beside
-// crlot_time_stretch in abi.cpp.
-#include <hip/hip_runtime.h>
+// crlot_time_stretch in stretch_host.cpp.
 
-#include <algorithm>
 #include <cmath>
-#include <cstdint>
-#include <mutex>
 #include <numeric>
-#include <string>
-#include <vector>
 
-#include "crlot_dsp.h"
-#include "kernels.h"
+#include "plan_internal.h"
 
-namespace crlot {
-int set_error(int code, const std::string& msg);  // abi.cpp: crlot_last_error()'s slot
-}
+using namespace crlot;
 
 struct crlot_resampler {
     crlot_resampler_desc desc{};
@@ -34,26 +25,9 @@ struct crlot_resampler {
 
 namespace {
 
-int fail(int code, const std::string& msg) { return crlot::set_error(code, msg); }
-int hip_fail(hipError_t e, const char* what) {
-    return fail(CRLOT_EHIP, std::string(what) + ": " + hipGetErrorString(e));
-}
-
 constexpr int64_t kMaxTable = int64_t(1) << 21;  // floats
 constexpr int64_t kMaxT = int64_t(1) << 48;      // T U stays far inside 64 bits
 constexpr double kPi = 3.14159265358979323846;
-
-struct DeviceGuard {
-    int prev = -1;
-    bool moved = false;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (dev >= 0 && dev != prev) moved = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceGuard() {
-        if (moved && prev >= 0) (void)hipSetDevice(prev);
-    }
-};
 
 struct Geo {
     int32_t U, D, W, K;
@@ -116,11 +90,6 @@ void fill_geometry(const crlot_resampler_desc& d, const Geo& g, crlot_resampler_
     out->device = d.device;
 }
 
-bool ranges_overlap(const float* a, int64_t a_len, const float* b, int64_t b_len) {
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return a0 < b0 + uintptr_t(b_len) * sizeof(float) && b0 < a0 + uintptr_t(a_len) * sizeof(float);
-}
-
 // the device table, uploaded once (caller holds r->mu, the device is current)
 int ensure_table(crlot_resampler* r) {
     if (r->d_table) return CRLOT_OK;
@@ -176,7 +145,7 @@ int resample_run(crlot_resampler* r, const float* d_x, float* d_y, int32_t n_str
     if (e == hipErrorNotSupported)
         return fail(CRLOT_EUNSUPPORTED, "the phase kernel does not take this filter (taps, U or span)");
     if (e == hipErrorInvalidValue) return fail(CRLOT_EUNSUPPORTED, "too many tiles for one call");
-    return e == hipSuccess ? CRLOT_OK : hip_fail(e, "resample kernel launch");
+    return launched(e, "resample kernel launch");
 }
 
 }  // namespace crlot
@@ -326,7 +295,7 @@ int crlot_resample(crlot_resampler* r, const float* d_x, float* d_y, int32_t n_s
     if (!d_x || !d_y) return fail(CRLOT_EINVAL, "null buffer");
     const int64_t L = out_len(r, T);
     if (ld_x < T || (n_streams > 1 && ld_y < L)) return fail(CRLOT_EINVAL, "leading dimension too small");
-    if (ranges_overlap(d_x, (n_streams - 1) * ld_x + T, d_y, (n_streams - 1) * ld_y + L))
+    if (overlap(d_x, (n_streams - 1) * ld_x + T, d_y, (n_streams - 1) * ld_y + L))
         return fail(CRLOT_EINVAL, "the input and output overlap");
     return crlot::resample_run(r, d_x, d_y, n_streams, T, L, ld_x, ld_y, static_cast<hipStream_t>(stream));
 }

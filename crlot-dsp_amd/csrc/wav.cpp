@@ -15,10 +15,7 @@
 #include <vector>
 
 #include "crlot_dsp.h"
-
-namespace crlot {
-int set_error(int code, const std::string& msg);  // abi.cpp: crlot_last_error()'s slot
-}
+#include "plan_internal.h"
 
 namespace {
 
