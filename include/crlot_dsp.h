@@ -28,6 +28,29 @@
  * so several host threads may also share a plan (the reference's KissFftPlan
  * is non-reentrant: kissfft_adapter.cc:256-263).  Streaming objects
  * (crlot_stream*, crlot_stream_rt*, crlot_ola*) are single-owner objects.
+ * The composite entries -- crlot_spectrogram where it is staged,
+ * crlot_time_stretch, crlot_pitch_shift, crlot_griffin_lim, crlot_hpss_masks,
+ * crlot_hpss and crlot_convolve (on the convolver's engine plan) -- keep their
+ * workspace (spectra, medians, masks, staged frames, chunk sums, uncropped
+ * outputs) in the calling stream's slot too, carved anew by every call; the
+ * staged crlot_roundtrip, crlot_stft and crlot_istft_ola and the chunked
+ * crlot_phase_vocoder carve the same buffer.  Nothing in it outlives the call
+ * that wrote it, and a call that needs more frees and reallocates it in stream
+ * order, behind the work already queued.  A plan keeps 16 slots: a call on a
+ * further stream takes over the least recently used one, and that one call
+ * waits for the whole device (hipDeviceSynchronize) before it frees the slot's
+ * buffers, since the evicted stream may have work in flight; a plan used from
+ * at most 16 streams never waits.
+ * Stream capture: once the stream's slot exists and is large enough -- after
+ * one call of the same shape on that stream (or crlot_plan_reserve_stream for
+ * the round trips), which also runs each launcher's one-time queries --
+ * crlot_roundtrip, crlot_spectrogram, crlot_time_stretch, crlot_pitch_shift,
+ * crlot_griffin_lim, crlot_hpss and crlot_convolve only launch kernels and asynchronous
+ * device-to-device copies and may be captured into a HIP graph and replayed;
+ * crlot_convolve and crlot_pitch_shift need crlot_convolver_prepare /
+ * crlot_resampler_prepare (or any earlier call) first, because the first use
+ * uploads the filter with synchronous copies.  A call that has to create,
+ * grow or recycle a slot must not be captured.
  */
 #ifndef CRLOT_DSP_H_
 #define CRLOT_DSP_H_
