@@ -126,6 +126,12 @@ class ConvolverLaunch(C.Structure):
                 ("chunk", C.c_int32), ("tile", C.c_int32), ("reserved", C.c_int32)]
 
 
+class SconvLaunch(C.Structure):
+    """crlot_sconv_launch (include/crlot_dsp.h): what a streaming convolver's last hop launched."""
+    _fields_ = [("head_kernel", C.c_int32), ("tail_kernel", C.c_int32), ("head_grid", C.c_int64),
+                ("tail_grid", C.c_int64), ("route", C.c_int32), ("tail_pending", C.c_int32)]
+
+
 class FftDesc(C.Structure):
     """crlot_fft_desc (include/crlot_dsp.h)."""
     _fields_ = [("domain", C.c_int32), ("nfft", C.c_int32), ("device", C.c_int32)]
@@ -203,6 +209,18 @@ def lib():
         "crlot_convolver_last_launch": ([vp, C.POINTER(ConvolverLaunch)], C.c_int),
         "crlot_fdl_mac": ([vp, vp, vp, i32, i64, i64, i64, i64, i64, i64, vp], C.c_int),
         "crlot_convolve": ([vp, vp, vp, i32, i64, i64, i64, vp], C.c_int),
+        "crlot_stream_convolver_create": ([vp, i32, C.POINTER(vp)], C.c_int),
+        "crlot_stream_convolver_destroy": ([vp], None),
+        "crlot_stream_convolver_prepare": ([vp], C.c_int),
+        "crlot_stream_convolver_state_bytes": ([vp], i64),
+        "crlot_stream_convolver_reset": ([vp], C.c_int),
+        "crlot_stream_convolver_set_layout": ([vp, i32], C.c_int),
+        "crlot_stream_convolver_set_route": ([vp, i32], C.c_int),
+        "crlot_stream_convolver_set_prefetch": ([vp, i32], C.c_int),
+        "crlot_stream_convolver_info": ([vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i64)], C.c_int),
+        "crlot_stream_convolver_last_launch": ([vp, C.POINTER(SconvLaunch)], C.c_int),
+        "crlot_stream_convolve_hop": ([vp, vp, vp, vp], C.c_int),
+        "crlot_stream_convolve_prefetch": ([vp, vp], C.c_int),
         "crlot_resample_geometry": ([C.POINTER(ResamplerDesc), C.POINTER(ResamplerGeometry)], C.c_int),
         "crlot_resample_table_host": ([C.POINTER(ResamplerDesc), fp], C.c_int),
         "crlot_rational_approx": ([C.c_double, i32, C.POINTER(i32), C.POINTER(i32)], C.c_int),
@@ -1538,6 +1556,122 @@ class Convolver:
         s = _stream_handle(x) if stream is None else stream
         _check(lib().crlot_convolve(self._h, x.data_ptr(), y.data_ptr(), S, T, ld_x, ld_y, s), "crlot_convolve")
         return y
+
+
+# ----------------------------------------------------------------- streaming convolution
+def _sconv_hop_layout(layout, device: int, channels: int, block: int, interleaved: bool, what: str = "block"):
+    """Validate one block of StreamConvolver.push from its plain description (shape,
+    strides in elements, dtype name, device index or None for a host tensor): a dense
+    float32 (channels, B) tensor, (B, channels) when interleaved, on `device`."""
+    shape, strides, dtype, dev = layout
+    want = (int(block), int(channels)) if interleaved else (int(channels), int(block))
+    if dtype != "float32":
+        raise ValueError(f"{what} must be float32, not {dtype}")
+    if dev is None:
+        raise ValueError(f"{what} must be a device tensor")
+    if int(dev) != int(device):
+        raise ValueError(f"{what} must live on the convolver's device {device}, not {dev}")
+    if tuple(int(v) for v in shape) != want:
+        raise ValueError(f"{what} must have shape {want}, not {tuple(shape)}")
+    # (the stride of a dimension of one element addresses nothing)
+    if any(n > 1 and int(st) != d for n, st, d in zip(want, strides, (want[1], 1))):
+        raise ValueError(f"{what} must be contiguous")
+    return want
+
+
+class StreamConvolver:
+    """crlot_convolve per hop with a carried delay line (crlot_stream_convolver_create /
+    crlot_stream_convolve_hop): push(block) takes B samples per channel and returns
+    block k of the full convolution of everything pushed so far, channel c with filter
+    c mod n_filters, bit for bit Convolver.convolve's samples with frame pairing off.
+    Blocks are (channels, B) float32 device tensors, (B, channels) when interleaved.
+    Keeps `conv` alive; creation touches no device."""
+
+    def __init__(self, conv: Convolver, channels: int, interleaved: bool = False):
+        self._h = None
+        if not isinstance(conv, Convolver):
+            raise ValueError("conv must be a Convolver")
+        self.conv, self.channels, self.interleaved = conv, int(channels), bool(interleaved)
+        h = C.c_void_p()
+        _check(lib().crlot_stream_convolver_create(conv._h, int(channels), C.byref(h)),
+               "crlot_stream_convolver_create")
+        self._h = h
+        _check(lib().crlot_stream_convolver_set_layout(self._h, int(self.interleaved)))
+        self.block, self.partitions = conv.block, conv.partitions
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().crlot_stream_convolver_destroy(self._h)
+            self._h = None
+        self.conv = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # interpreter shutdown
+            pass
+
+    def prepare(self):
+        """Prepare the convolver and allocate and zero the state now."""
+        with _torch().cuda.device(self.conv.device):
+            _check(lib().crlot_stream_convolver_prepare(self._h), "crlot_stream_convolver_prepare")
+
+    @property
+    def state_bytes(self) -> int:
+        return _check(int(lib().crlot_stream_convolver_state_bytes(self._h)), "crlot_stream_convolver_state_bytes")
+
+    @property
+    def hops(self) -> int:
+        n = C.c_int64()
+        _check(lib().crlot_stream_convolver_info(self._h, None, None, None, C.byref(n)), "crlot_stream_convolver_info")
+        return n.value
+
+    def reset(self):
+        _check(lib().crlot_stream_convolver_reset(self._h), "crlot_stream_convolver_reset")
+
+    def set_route(self, route: int = 0):
+        """0: the library's choice; 1: one launch per hop; 2: head + tail.  At hop 0 only."""
+        _check(lib().crlot_stream_convolver_set_route(self._h, int(route)), "crlot_stream_convolver_set_route")
+
+    def set_prefetch(self, automatic: bool = True):
+        _check(lib().crlot_stream_convolver_set_prefetch(self._h, int(bool(automatic))),
+               "crlot_stream_convolver_set_prefetch")
+
+    def last_launch(self) -> dict:
+        r = SconvLaunch()
+        _check(lib().crlot_stream_convolver_last_launch(self._h, C.byref(r)), "crlot_stream_convolver_last_launch")
+        d = {k: getattr(r, k) for k, _ in SconvLaunch._fields_}
+        d["head_name"] = kernel_name(r.head_kernel) if r.head_kernel else None
+        d["tail_name"] = kernel_name(r.tail_kernel) if r.tail_kernel else None
+        return d
+
+    def push(self, block, out=None, stream: int | None = None):
+        """block: one hop, or None for a block of zeros (a flush or a gap) -> out, output block k."""
+        torch = _torch()
+        dev = self.conv.device
+        shape = (self.block, self.channels) if self.interleaved else (self.channels, self.block)
+        if block is not None:
+            if not torch.is_tensor(block):
+                raise ValueError("block must be a float32 device tensor or None")
+            _sconv_hop_layout(_tensor_layout(block), dev, self.channels, self.block, self.interleaved)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=f"cuda:{dev}")
+        else:
+            if not torch.is_tensor(out):
+                raise ValueError("out must be a float32 device tensor")
+            _sconv_hop_layout(_tensor_layout(out), dev, self.channels, self.block, self.interleaved, "out")
+            if block is not None and _tensors_overlap(block, out):
+                raise ValueError("out overlaps block")
+        s = _stream_handle(out) if stream is None else stream
+        _check(lib().crlot_stream_convolve_hop(self._h, None if block is None else block.data_ptr(), out.data_ptr(),
+                                               s), "crlot_stream_convolve_hop")
+        return out
+
+    def prefetch(self, stream: int | None = None):
+        """Manual prefetch: enqueue the tail of the last hop (nothing when none is pending)."""
+        if stream is None:
+            stream = _torch().cuda.current_stream(self.conv.device).cuda_stream
+        _check(lib().crlot_stream_convolve_prefetch(self._h, stream), "crlot_stream_convolve_prefetch")
 
 
 class FftPlan:

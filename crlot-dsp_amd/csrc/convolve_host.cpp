@@ -109,7 +109,7 @@ int convolver_ready(crlot_convolver* c, ConvolverShape& out) {
     std::lock_guard<std::mutex> lk(c->mu);
     const int rc = ensure_ready(c);
     if (rc != CRLOT_OK) return rc;
-    out = ConvolverShape{c->B, c->P, c->device, c->K, c->plan};
+    out = ConvolverShape{c->B, c->P, c->device, c->K, c->plan, c->desc.n_filters, c->d_h};
     return CRLOT_OK;
 }
 

@@ -639,11 +639,38 @@ struct ConvolverShape {
     int32_t B, P, device;
     int64_t K;
     crlot_plan* plan;
+    int32_t n_filters;
+    const float* d_h;  // the filter spectra on the device, [n_filters][P][N + 2]
 };
 int convolver_ready(crlot_convolver* c, ConvolverShape& out);
 int fdl_mac_run(crlot_convolver* c, const float* d_in, float* d_out, int32_t n_streams, int64_t F_in, int64_t F_out,
                 int64_t ld_in, int64_t ldf_in, int64_t ld_out, int64_t ldf_out, hipStream_t s,
                 int32_t first_stream = 0);
+
+// ---- stream_convolve.hip: one hop of the streaming convolver (crlot_stream_convolve_hop; the contract is in include/crlot_dsp.h)
+// Per channel: ring [parts][N + 2] (hop j's spectrum in row j mod parts), pre [N + 2]
+// (the raw partial chain of the next frame, written by the tail), carry [B] (the upper
+// half of the last frame).  Channel c reads filter c mod n_filters of h.  t: the engine
+// plan's tables (the pass and super twiddles are read).
+struct SconvArgs {
+    DevTables t;
+    const float* in;  // the hop: channel c sample i at in[c*in_ld + i*in_inc]; nullptr: zeros
+    float* out;       // block k, same layout
+    int64_t in_ld, in_inc, out_ld, out_inc;
+    float* ring;
+    float* pre;
+    float* carry;
+    const float* h;
+    int64_t k;        // head: the hop; tail: the frame whose partial chain it forms
+    int32_t channels, block, parts, n_filters;
+    float inv_n;
+};
+// K_sconv_head: hop k -> X_k into the ring, the chain's last term on pre (inline_chain:
+// the whole chain over the ring, pre not read), inverse, overlap-add with the carry,
+// block k.  K_sconv_tail: pre for frame a.k from the ring.  *grid: workgroups launched.
+// hipErrorInvalidValue: a block outside 128 / 256 / 512 / 1024 or a grid beyond 2^31-1.
+hipError_t launch_sconv_head(const SconvArgs& a, bool inline_chain, int64_t* grid, hipStream_t s);
+hipError_t launch_sconv_tail(const SconvArgs& a, int64_t* grid, hipStream_t s);
 
 // dsp::FrameQueue frames on the device: [stream][F][N] from x [stream][ld_x]
 hipError_t launch_fq_frames(const float* x, int64_t T, int64_t ld_x, int n_streams, float* frames, int64_t F,

@@ -184,6 +184,8 @@ extern "C" const char* crlot_kernel_name(int32_t id) {
         case CRLOT_K_HPSS_FREQ: return "k_hpss_freq";
         case CRLOT_K_HPSS_TIME: return "k_hpss_time";
         case CRLOT_K_FDL_MAC: return "k_fdl_mac";
+        case CRLOT_K_SCONV_HEAD: return "k_sconv_head";
+        case CRLOT_K_SCONV_TAIL: return "k_sconv_tail";
         case CRLOT_K_EXPERIMENT: return "k_experiment";
         default: return "unknown";
     }

@@ -265,7 +265,10 @@ int crlot_test_inject(int32_t what, int32_t count);
 #define CRLOT_K_HPSS_TIME 43    /* crlot_hpss_masks: the running median along time, then the masks */
 /* (44 is not assigned: crlot_kernel_name(44) stays "unknown") */
 #define CRLOT_K_FDL_MAC 45      /* crlot_fdl_mac: the frequency-domain delay line of crlot_convolve */
-#define CRLOT_K_EXPERIMENT 99    /* experiment builds only */
+/* (46 is not assigned: crlot_kernel_name(46) stays "unknown") */
+#define CRLOT_K_SCONV_HEAD 47   /* crlot_stream_convolve_hop: the hop, the chain's last term (or all of it), block k */
+#define CRLOT_K_SCONV_TAIL 48   /* ... the next frame's partial chain, off the critical path */
+#define CRLOT_K_EXPERIMENT 99   /* experiment builds only */
 typedef struct crlot_launch_info {
     int32_t n_kernels;
     int32_t kernels[8];
@@ -929,6 +932,91 @@ int crlot_fdl_mac(crlot_convolver* c, const float* d_spec_in, float* d_spec_out,
                   int64_t F_out, int64_t ld_in, int64_t ldf_in, int64_t ld_out, int64_t ldf_out, void* stream);
 int crlot_convolve(crlot_convolver* c, const float* d_x, float* d_y, int32_t n_streams, int64_t T, int64_t ld_x,
                    int64_t ld_y, void* stream);
+
+/* ---------------------------------------------------------------- streaming convolution
+ * crlot_convolve per hop, with a carried delay line: a crlot_stream_convolver over a
+ * crlot_convolver (block B, P partitions, spectra H) is fed B samples per channel per
+ * call, and call k writes output block k: samples [kB, (k+1)B) of the full
+ * convolution of everything pushed so far with filter c mod n_filters.  The latency
+ * is B samples and every call emits.  Supported blocks: B in {128, 256, 512, 1024}
+ * (N = 2B on the register-resident hop kernels); any other block the convolver
+ * accepts is CRLOT_EUNSUPPORTED at create.
+ *
+ * Values.  Output block k of channel c equals, bit for bit, samples [kB, (k+1)B) of
+ * row c of crlot_convolve over the concatenated input with frame pairing off on the
+ * engine plan, for the caller's blocks and for any zero blocks after them.  Per
+ * channel c and hop k, q = c mod n_filters:
+ *   analysis   x = sanitize(block) zero-padded to N = 2B; X_k = the per-frame forward
+ *              transform and kiss_fftr split (crlot_stft's row k on the engine plan
+ *              with pairing 0 = crlot_rfft_batched of the padded block), kept in row
+ *              k mod P of a per-channel ring of P spectrum rows;
+ *   delay line crlot_fdl_mac's chain for f = k, F_in = k + 1: from re = im = +0, for
+ *              j = max(0, k-P+1) .. k ascending, p = k - j, the four fmaf in that
+ *              order on H[q][p] and X_j, then + 0.0f;
+ *   synthesis  kiss_fftri merge, inverse transform, * 1/N, sanitize, overlap-add as
+ *              crlot_istft_ola on the engine plan (fma(fma(o, ws, 0), g, acc), then
+ *              the division by the norm; ws = g = norm = 1): the first B samples plus
+ *              the B samples carried from frame k-1 are block k, the last B samples
+ *              the new carry.
+ * d_hop_in = NULL is a block of zeros (the flush after the input ends, or a gap): the
+ * bits are those of crlot_convolve, where rows j >= F_in are not loaded, because an
+ * accumulator that starts at +0 never becomes -0 and adding the +-0 products of a
+ * zero row to it changes nothing (H is finite: create checks the taps).  The hop
+ * path has no frame pairs.
+ *
+ * Routes.  In frame k's chain only the last term depends on hop k.  Route 2: the hop
+ * launches CRLOT_K_SCONV_HEAD, which adds that term to a partial chain formed
+ * before the hop arrived, and CRLOT_K_SCONV_TAIL forms the next frame's partial
+ * chain behind it, so a hop's latency does not grow with the filter.  With automatic
+ * prefetch (the default) the hop enqueues the tail on the same stream; after
+ * crlot_stream_convolver_set_prefetch(sc, 0) crlot_stream_convolve_prefetch does, on
+ * the stream it is given (the caller orders it behind the head and in front of the
+ * next hop), and a hop that finds the tail not enqueued runs it in front of its head.
+ * crlot_stream_convolve_prefetch with nothing pending, or on route 1, is CRLOT_OK
+ * and launches nothing.  Route 1: the head runs the whole chain, one launch, no
+ * partial chain.  P = 1 is always route 1; the library's choice (route 0) is route 1
+ * at P = 2 with B <= 512, where one launch measured the lower median hop, and
+ * route 2 otherwise.  crlot_stream_convolver_set_route is allowed at hop 0 only, after
+ * create or reset (else CRLOT_ERUNTIME).  The bits never depend on the route, the
+ * prefetch mode, the channel count, a channel's position or the layout.
+ *
+ * The object borrows the convolver, which must outlive it; leave the engine plan's
+ * tables alone.  crlot_stream_convolver_create touches no device and works on an
+ * unprepared convolver (CRLOT_EINVAL: a null argument, channels < 1, a state size or
+ * grid that does not fit).  crlot_stream_convolver_prepare, or the first hop,
+ * prepares the convolver and allocates and zeroes the state: per channel the ring
+ * [P][N+2], the partial chain [N+2] and the carry [B], floats
+ * (crlot_stream_convolver_state_bytes, valid before prepare; CRLOT_ENOMEM when it does
+ * not fit).  A single-owner object like crlot_stream: the hops of one object go on
+ * one stream or are ordered by the caller.  Graph capture is not supported (the hop
+ * index is a by-value kernel argument).  Blocks are channel-major [channels][B], or
+ * [B][channels] after crlot_stream_convolver_set_layout(sc, 1).
+ * crlot_stream_convolver_reset synchronises the device, zeroes the state and the hop
+ * counter and clears a pending tail.  crlot_stream_convolve_hop: CRLOT_EINVAL for a
+ * null sc or d_hop_out, or a d_hop_out that overlaps d_hop_in. */
+typedef struct crlot_stream_convolver crlot_stream_convolver;
+typedef struct crlot_sconv_launch {
+    int32_t head_kernel;   /* CRLOT_K_SCONV_HEAD; 0: no hop yet */
+    int32_t tail_kernel;   /* CRLOT_K_SCONV_TAIL; 0: no tail (yet) */
+    int64_t head_grid;     /* workgroups: ceil(channels / 4) */
+    int64_t tail_grid;     /* workgroups: channels * ceil((B + 1) / 64) */
+    int32_t route;         /* 1 one launch, 2 head + tail */
+    int32_t tail_pending;  /* manual prefetch: the tail of the last hop is not enqueued yet */
+} crlot_sconv_launch;
+int crlot_stream_convolver_create(crlot_convolver* c, int32_t channels, crlot_stream_convolver** out);
+void crlot_stream_convolver_destroy(crlot_stream_convolver* sc);
+int crlot_stream_convolver_prepare(crlot_stream_convolver* sc);
+int64_t crlot_stream_convolver_state_bytes(const crlot_stream_convolver* sc);
+int crlot_stream_convolver_reset(crlot_stream_convolver* sc);
+int crlot_stream_convolver_set_layout(crlot_stream_convolver* sc, int32_t interleaved);
+int crlot_stream_convolver_set_route(crlot_stream_convolver* sc, int32_t route /* 0 library's choice, 1, 2 */);
+int crlot_stream_convolver_set_prefetch(crlot_stream_convolver* sc, int32_t automatic /* default 1 */);
+int crlot_stream_convolver_info(const crlot_stream_convolver* sc, int32_t* channels, int32_t* block, int32_t* P,
+                                int64_t* hops);
+int crlot_stream_convolver_last_launch(const crlot_stream_convolver* sc, crlot_sconv_launch* out);
+int crlot_stream_convolve_hop(crlot_stream_convolver* sc, const float* d_hop_in /* NULL: zeros */, float* d_hop_out,
+                              void* stream);
+int crlot_stream_convolve_prefetch(crlot_stream_convolver* sc, void* stream);
 
 /* host helpers (no device) */
 #define CRLOT_MEL_HTK 0

@@ -245,6 +245,61 @@ class Convolver {
     crlot_convolver* c_ = nullptr;
 };
 
+// crlot_convolve per hop with a carried delay line (crlot_stream_convolver_*): every
+// push takes `block` samples per channel and writes block k of the full convolution
+// of everything pushed so far.  Borrows the Convolver, which must outlive it.
+class StreamConvolver {
+   public:
+    StreamConvolver(Convolver& conv, int channels, bool interleaved = false) {
+        check(crlot_stream_convolver_create(conv.get(), channels, &s_), "crlot_stream_convolver_create");
+        check(crlot_stream_convolver_set_layout(s_, interleaved ? 1 : 0), "crlot_stream_convolver_set_layout");
+    }
+    ~StreamConvolver() { crlot_stream_convolver_destroy(s_); }
+    StreamConvolver(const StreamConvolver&) = delete;
+    StreamConvolver& operator=(const StreamConvolver&) = delete;
+    StreamConvolver(StreamConvolver&& o) noexcept : s_(o.s_) { o.s_ = nullptr; }
+    StreamConvolver& operator=(StreamConvolver&& o) noexcept {
+        if (this != &o) {
+            crlot_stream_convolver_destroy(s_);
+            s_ = o.s_;
+            o.s_ = nullptr;
+        }
+        return *this;
+    }
+    void prepare() { check(crlot_stream_convolver_prepare(s_), "crlot_stream_convolver_prepare"); }
+    void reset() { check(crlot_stream_convolver_reset(s_), "crlot_stream_convolver_reset"); }
+    // 0: the library's choice, 1: one launch per hop, 2: head + tail; at hop 0 only
+    void set_route(int route) { check(crlot_stream_convolver_set_route(s_, route), "crlot_stream_convolver_set_route"); }
+    void set_prefetch(bool automatic) {
+        check(crlot_stream_convolver_set_prefetch(s_, automatic ? 1 : 0), "crlot_stream_convolver_set_prefetch");
+    }
+    int64_t state_bytes() const {
+        const int64_t n = crlot_stream_convolver_state_bytes(s_);
+        check(n < 0 ? int(n) : 0, "crlot_stream_convolver_state_bytes");
+        return n;
+    }
+    int64_t hops() const {
+        int64_t n = 0;
+        check(crlot_stream_convolver_info(s_, nullptr, nullptr, nullptr, &n), "crlot_stream_convolver_info");
+        return n;
+    }
+    crlot_sconv_launch last_launch() const {
+        crlot_sconv_launch r{};
+        check(crlot_stream_convolver_last_launch(s_, &r), "crlot_stream_convolver_last_launch");
+        return r;
+    }
+    // d_in (nullptr: a block of zeros) and d_out: [channels][block] floats, [block][channels] when interleaved
+    void push_device(const float* d_in, float* d_out, hipStream_t s = nullptr) {
+        check(crlot_stream_convolve_hop(s_, d_in, d_out, s), "crlot_stream_convolve_hop");
+    }
+    // manual prefetch: the tail of the last hop (nothing when none is pending)
+    void prefetch(hipStream_t s = nullptr) { check(crlot_stream_convolve_prefetch(s_, s), "crlot_stream_convolve_prefetch"); }
+    crlot_stream_convolver* get() const { return s_; }
+
+   private:
+    crlot_stream_convolver* s_ = nullptr;
+};
+
 // Batched round trip: n_streams mono streams, each T samples.
 class StftEngine {
    public:
