@@ -132,6 +132,13 @@ class SconvLaunch(C.Structure):
                 ("tail_grid", C.c_int64), ("route", C.c_int32), ("tail_pending", C.c_int32)]
 
 
+class FdafLaunch(C.Structure):
+    """crlot_fdaf_launch (include/crlot_dsp.h): what an adaptive filter's last hop launched."""
+    _fields_ = [("hop_kernel", C.c_int32), ("update_kernel", C.c_int32), ("constrain_kernel", C.c_int32),
+                ("reserved", C.c_int32), ("hop_grid", C.c_int64), ("update_grid", C.c_int64),
+                ("constrain_grid", C.c_int64)]
+
+
 class FftDesc(C.Structure):
     """crlot_fft_desc (include/crlot_dsp.h)."""
     _fields_ = [("domain", C.c_int32), ("nfft", C.c_int32), ("device", C.c_int32)]
@@ -221,6 +228,23 @@ def lib():
         "crlot_stream_convolver_last_launch": ([vp, C.POINTER(SconvLaunch)], C.c_int),
         "crlot_stream_convolve_hop": ([vp, vp, vp, vp], C.c_int),
         "crlot_stream_convolve_prefetch": ([vp, vp], C.c_int),
+        "crlot_fdaf_create": ([i32, i64, i32, C.POINTER(vp)], C.c_int),
+        "crlot_fdaf_destroy": ([vp], None),
+        "crlot_fdaf_prepare": ([vp], C.c_int),
+        "crlot_fdaf_state_bytes": ([vp], i64),
+        "crlot_fdaf_reset": ([vp], C.c_int),
+        "crlot_fdaf_set_layout": ([vp, i32], C.c_int),
+        "crlot_fdaf_info": ([vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i64), C.POINTER(i32), C.POINTER(i64)],
+                            C.c_int),
+        "crlot_fdaf_last_launch": ([vp, C.POINTER(FdafLaunch)], C.c_int),
+        "crlot_fdaf_set_step": ([vp, C.c_double, C.c_double, C.c_double], C.c_int),
+        "crlot_fdaf_set_constraint": ([vp, i32], C.c_int),
+        "crlot_fdaf_set_adapt": ([vp, i32], C.c_int),
+        "crlot_fdaf_set_taps": ([vp, fp, i32, i64], C.c_int),
+        "crlot_fdaf_get_taps": ([vp, fp, i64], C.c_int),
+        "crlot_fdaf_state": ([vp] + [C.POINTER(vp)] * 6, C.c_int),
+        "crlot_fdaf_hop": ([vp, vp, vp, vp, vp, vp], C.c_int),
+        "crlot_fdaf_constrain": ([vp, i32, vp], C.c_int),
         "crlot_resample_geometry": ([C.POINTER(ResamplerDesc), C.POINTER(ResamplerGeometry)], C.c_int),
         "crlot_resample_table_host": ([C.POINTER(ResamplerDesc), fp], C.c_int),
         "crlot_rational_approx": ([C.c_double, i32, C.POINTER(i32), C.POINTER(i32)], C.c_int),
@@ -1672,6 +1696,162 @@ class StreamConvolver:
         if stream is None:
             stream = _torch().cuda.current_stream(self.conv.device).cuda_stream
         _check(lib().crlot_stream_convolve_prefetch(self._h, stream), "crlot_stream_convolve_prefetch")
+
+
+# ----------------------------------------------------------------- adaptive filter
+class _DeviceFloats:
+    """A float32 array in device memory for torch.as_tensor (the CUDA array interface)."""
+
+    def __init__(self, ptr: int, shape):
+        self.__cuda_array_interface__ = {"shape": tuple(int(n) for n in shape), "typestr": "<f4",
+                                         "data": (int(ptr), False), "version": 2, "strides": None}
+
+
+class AdaptiveFilter:
+    """The partitioned-block frequency-domain adaptive filter (crlot_fdaf_create /
+    crlot_fdaf_hop): push(x, d) takes B samples per channel of the reference x and of the
+    desired signal d and returns the error e = d - y, y the output of a K-tap filter
+    per channel that adapts to make e small.  Blocks are (channels, B) float32 device
+    tensors, (B, channels) when interleaved.  Creation touches no device; the state
+    lives on the device that is current at prepare() or at the first call needing it."""
+
+    def __init__(self, block: int, taps: int, channels: int, interleaved: bool = False):
+        self._h = None
+        h = C.c_void_p()
+        _check(lib().crlot_fdaf_create(int(block), int(taps), int(channels), C.byref(h)), "crlot_fdaf_create")
+        self._h = h
+        self.block, self.taps_count, self.channels, self.interleaved = int(block), int(taps), int(channels), bool(interleaved)
+        self.partitions = -(-int(taps) // int(block))
+        self.bins = int(block) + 1
+        self._device = None
+        _check(lib().crlot_fdaf_set_layout(self._h, int(self.interleaved)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().crlot_fdaf_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # interpreter shutdown
+            pass
+
+    @property
+    def device(self) -> int:
+        """The device of the state (the current device until the state exists)."""
+        if self._device is None:
+            return int(_torch().cuda.current_device())
+        return self._device
+
+    def prepare(self):
+        """Make the internal plan and allocate and zero the state now, on the current device."""
+        if self._device is None:
+            dev = int(_torch().cuda.current_device())
+            _check(lib().crlot_fdaf_prepare(self._h), "crlot_fdaf_prepare")
+            self._device = dev
+
+    @property
+    def state_bytes(self) -> int:
+        return _check(int(lib().crlot_fdaf_state_bytes(self._h)), "crlot_fdaf_state_bytes")
+
+    @property
+    def hops(self) -> int:
+        n = C.c_int64()
+        _check(lib().crlot_fdaf_info(self._h, None, None, None, None, C.byref(n)), "crlot_fdaf_info")
+        return n.value
+
+    def reset(self):
+        """Zero the state (the weights too) and the hop counter."""
+        _check(lib().crlot_fdaf_reset(self._h), "crlot_fdaf_reset")
+
+    def set_step(self, mu: float = 0.5, lam: float = 0.9, delta: float = 1e-3):
+        _check(lib().crlot_fdaf_set_step(self._h, float(mu), float(lam), float(delta)), "crlot_fdaf_set_step")
+
+    def set_constraint(self, mode: int = 1):
+        """0: none; 1: round-robin, partition k mod P after hop k; 2: every partition every hop."""
+        _check(lib().crlot_fdaf_set_constraint(self._h, int(mode)), "crlot_fdaf_set_constraint")
+
+    def set_adapt(self, on: bool = True):
+        _check(lib().crlot_fdaf_set_adapt(self._h, int(bool(on))), "crlot_fdaf_set_adapt")
+
+    def set_taps(self, h):
+        """h: (K,) or (1, K) for every channel, or (channels, K), host float32."""
+        h = np.ascontiguousarray(h, np.float32)
+        h = h[None] if h.ndim == 1 else h
+        if h.ndim != 2 or h.shape[1] != self.taps_count or h.shape[0] not in (1, self.channels):
+            raise ValueError(f"taps must have shape ({self.taps_count},), (1, {self.taps_count}) or "
+                             f"({self.channels}, {self.taps_count}), not {h.shape}")
+        self.prepare()
+        with _torch().cuda.device(self._device):
+            _check(lib().crlot_fdaf_set_taps(self._h, _fptr(h), h.shape[0], h.shape[1]), "crlot_fdaf_set_taps")
+
+    def taps(self) -> np.ndarray:
+        """The filters in the time domain, (channels, K) float32, from the device."""
+        self.prepare()
+        out = np.zeros((self.channels, self.taps_count), np.float32)
+        with _torch().cuda.device(self._device):
+            _check(lib().crlot_fdaf_get_taps(self._h, _fptr(out), self.taps_count), "crlot_fdaf_get_taps")
+        return out
+
+    def state(self) -> dict:
+        """The state on the device as float32 torch views (valid while this object lives, zeroed
+        by reset): ring and W (channels, P, 2 (B+1)), E and G (channels, 2 (B+1)) as (re, im)
+        pairs, pw (channels, B+1), prev (channels, B)."""
+        torch = _torch()
+        self.prepare()
+        ptrs = [C.c_void_p() for _ in range(6)]
+        _check(lib().crlot_fdaf_state(self._h, *[C.byref(p) for p in ptrs]), "crlot_fdaf_state")
+        Cn, P, row, B = self.channels, self.partitions, 2 * self.bins, self.block
+        shapes = {"ring": (Cn, P, row), "W": (Cn, P, row), "pw": (Cn, self.bins), "E": (Cn, row), "G": (Cn, row),
+                  "prev": (Cn, B)}
+        with torch.cuda.device(self._device):
+            return {name: torch.as_tensor(_DeviceFloats(p.value, shape), device=f"cuda:{self._device}")
+                    for (name, shape), p in zip(shapes.items(), ptrs)}
+
+    def last_launch(self) -> dict:
+        r = FdafLaunch()
+        _check(lib().crlot_fdaf_last_launch(self._h, C.byref(r)), "crlot_fdaf_last_launch")
+        d = {k: getattr(r, k) for k, _ in FdafLaunch._fields_ if k != "reserved"}
+        d["kernels"] = [kid for kid in (r.hop_kernel, r.update_kernel, r.constrain_kernel) if kid]
+        d["names"] = [kernel_name(kid) for kid in d["kernels"]]
+        return d
+
+    def _block(self, t, what):
+        if not _torch().is_tensor(t):
+            raise ValueError(f"{what} must be a float32 device tensor")
+        _sconv_hop_layout(_tensor_layout(t), self.device, self.channels, self.block, self.interleaved, what)
+        return t
+
+    def push(self, x, d, e=None, y=None, stream: int | None = None):
+        """x: the reference block, or None for a block of zeros; d: the desired block.  Returns
+        e = d - y; y (optional) receives the filter's output."""
+        torch = _torch()
+        if x is not None:
+            self._block(x, "x")
+        self._block(d, "d")
+        if e is None:
+            e = torch.empty_like(d)
+        else:
+            self._block(e, "e")
+        if y is not None:
+            self._block(y, "y")
+        ins = [t for t in (x, d) if t is not None]
+        if any(_tensors_overlap(i, o) for i in ins for o in (e, y) if o is not None) or \
+                (y is not None and _tensors_overlap(e, y)):
+            raise ValueError("an output block overlaps another block")
+        self.prepare()
+        s = _stream_handle(d) if stream is None else stream
+        _check(lib().crlot_fdaf_hop(self._h, None if x is None else x.data_ptr(), d.data_ptr(), e.data_ptr(),
+                                    None if y is None else y.data_ptr(), s), "crlot_fdaf_hop")
+        return e
+
+    def constrain(self, p: int = -1, stream: int | None = None):
+        """The gradient constraint alone on partition p of every channel (-1: every partition)."""
+        self.prepare()
+        if stream is None:
+            stream = _torch().cuda.current_stream(self._device).cuda_stream
+        _check(lib().crlot_fdaf_constrain(self._h, int(p), stream), "crlot_fdaf_constrain")
 
 
 class FftPlan:

@@ -672,6 +672,38 @@ struct SconvArgs {
 hipError_t launch_sconv_head(const SconvArgs& a, bool inline_chain, int64_t* grid, hipStream_t s);
 hipError_t launch_sconv_tail(const SconvArgs& a, int64_t* grid, hipStream_t s);
 
+// ---- fdaf.hip: one hop of the adaptive filter (crlot_fdaf_hop; the contract is in include/crlot_dsp.h)
+// Per channel: ring [parts][N + 2] (hop j's reference spectrum in row j mod parts), w
+// [parts][N + 2] (the weight spectra), espec and g [N + 2] (the last hop's error spectrum
+// and gradient), prev [B] (the last reference block, sanitized), pw [B + 1] (the power
+// estimate).  t: the internal plan's tables (the pass and super twiddles are read).
+struct FdafArgs {
+    DevTables t;
+    const float* x;   // the reference block: channel c sample i at x[c*ld + i*inc]; nullptr: zeros
+    const float* d;   // the desired block, same layout
+    float* e;         // out: d - y
+    float* y;         // out: the filter's output; nullptr: not stored
+    int64_t ld, inc;
+    float* ring;
+    float* w;
+    float* espec;
+    float* g;
+    float* prev;
+    float* pw;
+    int64_t k;        // the hop
+    int32_t channels, block, parts;
+    int32_t adapt;    // hop: form E and G as well
+    int32_t p_first, p_count;  // constrain: partitions p_first .. p_first + p_count - 1 of every channel
+    float inv_n;
+    float mu_p, lambda, omega, delta;
+};
+// K_fdaf_hop: steps 1 - 6 of the contract.  K_fdaf_update: step 7 for hop a.k.
+// K_fdaf_constrain: step 8 on the partitions a.p_first ...  *grid: workgroups launched.
+// hipErrorInvalidValue: a block outside 128 / 256 / 512 / 1024 or a grid beyond 2^31-1.
+hipError_t launch_fdaf_hop(const FdafArgs& a, int64_t* grid, hipStream_t s);
+hipError_t launch_fdaf_update(const FdafArgs& a, int64_t* grid, hipStream_t s);
+hipError_t launch_fdaf_constrain(const FdafArgs& a, int64_t* grid, hipStream_t s);
+
 // dsp::FrameQueue frames on the device: [stream][F][N] from x [stream][ld_x]
 hipError_t launch_fq_frames(const float* x, int64_t T, int64_t ld_x, int n_streams, float* frames, int64_t F,
                             int64_t N, int64_t H, int64_t pad, int pad_mode, hipStream_t s);

@@ -186,6 +186,9 @@ extern "C" const char* crlot_kernel_name(int32_t id) {
         case CRLOT_K_FDL_MAC: return "k_fdl_mac";
         case CRLOT_K_SCONV_HEAD: return "k_sconv_head";
         case CRLOT_K_SCONV_TAIL: return "k_sconv_tail";
+        case CRLOT_K_FDAF_HOP: return "k_fdaf_hop";
+        case CRLOT_K_FDAF_UPDATE: return "k_fdaf_update";
+        case CRLOT_K_FDAF_CONSTRAIN: return "k_fdaf_constrain";
         case CRLOT_K_EXPERIMENT: return "k_experiment";
         default: return "unknown";
     }

@@ -268,6 +268,9 @@ int crlot_test_inject(int32_t what, int32_t count);
 /* (46 is not assigned: crlot_kernel_name(46) stays "unknown") */
 #define CRLOT_K_SCONV_HEAD 47   /* crlot_stream_convolve_hop: the hop, the chain's last term (or all of it), block k */
 #define CRLOT_K_SCONV_TAIL 48   /* ... the next frame's partial chain, off the critical path */
+#define CRLOT_K_FDAF_HOP 49     /* crlot_fdaf_hop: filter, error, power estimate, error spectrum and gradient */
+#define CRLOT_K_FDAF_UPDATE 50  /* ... the weight update over the partitions */
+#define CRLOT_K_FDAF_CONSTRAIN 51 /* ... the gradient constraint (crlot_fdaf_constrain) */
 #define CRLOT_K_EXPERIMENT 99   /* experiment builds only */
 typedef struct crlot_launch_info {
     int32_t n_kernels;
@@ -1017,6 +1020,111 @@ int crlot_stream_convolver_last_launch(const crlot_stream_convolver* sc, crlot_s
 int crlot_stream_convolve_hop(crlot_stream_convolver* sc, const float* d_hop_in /* NULL: zeros */, float* d_hop_out,
                               void* stream);
 int crlot_stream_convolve_prefetch(crlot_stream_convolver* sc, void* stream);
+
+/* ---------------------------------------------------------------- adaptive filter
+ * The partitioned-block frequency-domain adaptive filter (PBFDAF, overlap-save; Speex's
+ * MDF is the best-known instance): per channel a filter of K taps, held as P =
+ * ceil(K / B) weight spectra W_p of N = 2B points, is run on a reference x and adapted
+ * so that its output y follows a desired signal d.  Each call takes B samples of x
+ * and d per channel and writes the B samples of the error e = d - y (and of y when
+ * asked): echo and feedback cancellation, system identification, noise cancellation
+ * with a reference.  The latency is B samples and every call emits.  Supported
+ * blocks: B in {128, 256, 512, 1024} (crlot_stream_convolve_hop's register-resident
+ * transforms; the B = 1024 instantiation builds without scratch); any other block a
+ * plan accepts is CRLOT_EUNSUPPORTED; a block no plan accepts is CRLOT_EINVAL.
+ *
+ * Values.  float32 throughout; per channel and hop k, counted from create / reset:
+ *   1  xb = sanitize(x block) (x = NULL: zeros), db = sanitize(d block);
+ *   2  the frame [prev, xb], no window; X_k = the per-frame forward transform and
+ *      kiss_fftr split, stored in row k mod P of a ring of P spectrum rows; then prev =
+ *      xb.  X_k equals, bit for bit, row k of crlot_stft with frame pairing off on a
+ *      plan with frame N = 2B, hop B and a window of ones, over the reference prefixed
+ *      by B zeros (= crlot_rfft_batched of the frame on that plan);
+ *   3  Y from re = im = +0, for j = max(0, k-P+1) .. k ascending, p = k - j: the
+ *      streaming convolver's four fmaf with H := W_p and X_j, then + 0.0f.  Rows of
+ *      hops that have not happened are not read;
+ *   4  o = sanitize(inverse(kiss_fftri merge(Y)) * 1/N); y = o[B .. 2B); e = db - y, one
+ *      subtraction; e is stored, y when d_y is not NULL;
+ *   5  adapting: E = the forward transform and split of the frame [+0 x B, e], sanitized
+ *      as every forward entry sanitizes its input (= crlot_rfft_batched of that frame);
+ *   6  per bin: m = (Xr Xr) + (Xi Xi); pw = m at k = 0, else (lambda pw) + (omega m),
+ *      whether adapting or not.  Adapting: g = mu_P / (pw + delta), G = (g Er, g Ei).
+ *      Every product, sum and quotient is rounded on its own (no FMA), the division
+ *      correctly rounded;
+ *   7  adapting, every p with k - p >= 0 and every bin, X = ring row (k - p) mod P:
+ *        re = fmaf(Xr, Gr, Wr); re = fmaf(Xi, Gi, re);
+ *        im = fmaf(Xr, Gi, Wi); im = fmaf(-Xi, Gr, im);     (W_p += conj(X) G)
+ *   8  adapting, the gradient constraint on partition k mod P (mode 1) or on every
+ *      partition (mode 2): w = inverse(merge(W_p)) * 1/N; w[B .. 2B) = +0; W_p = forward
+ *      and split of w (no sanitize in either direction).
+ * The constants are set by crlot_fdaf_set_step(mu, lambda, delta), defaults 0.5, 0.9,
+ * 1e-3: mu_P = float32(mu / P) and omega = float32(1 - lambda), both formed in double,
+ * lambda and delta rounded to float32 (CRLOT_EINVAL unless 0 <= mu <= 2, 0 <= lambda < 1,
+ * delta > 0, all finite).  crlot_fdaf_set_constraint: 0 none, 1 round-robin (default),
+ * 2 every partition every hop.  crlot_fdaf_set_adapt(af, 0) freezes the filter: steps
+ * 1 - 4 and the power estimate of step 6 alone.  The bits of e, y and the state never
+ * depend on the channel count, a channel's position, the layout or the constraint
+ * kernel's grid: mode 1 equals mode 0 hops each followed by crlot_fdaf_constrain(af,
+ * k mod P), mode 2 equals mode 0 hops each followed by crlot_fdaf_constrain(af, -1).
+ *
+ * Kernels.  A hop enqueues, on the caller's stream, CRLOT_K_FDAF_HOP (steps 1 - 6, one
+ * wave per channel; e and y are complete after it), then when adapting
+ * CRLOT_K_FDAF_UPDATE (step 7, one wave per 64 bins of a channel) and, in modes 1 and
+ * 2, CRLOT_K_FDAF_CONSTRAIN (step 8, one wave per channel and partition).
+ * crlot_fdaf_last_launch lists the last hop's.  crlot_fdaf_constrain(af, p, stream)
+ * runs step 8 alone on partition p of every channel, or on all partitions with p = -1
+ * (CRLOT_EINVAL: p outside -1 .. P-1).
+ *
+ * Taps.  crlot_fdaf_set_taps(af, h, n_rows, ld) loads K taps per channel from host
+ * rows ld >= K floats apart (n_rows = channels, or 1: one row for every channel;
+ * CRLOT_EINVAL otherwise or for a tap that is not finite): W_p = crlot_rfft_batched of
+ * partition p zero-padded to N on the internal plan, as a crlot_convolver's spectra.
+ * crlot_fdaf_get_taps(af, out, ld) writes K floats per channel: the first B samples of
+ * crlot_irfft_batched of each W_p, partition after partition.  Both synchronise the
+ * device.  crlot_fdaf_state returns the device pointers of the state (any may be NULL):
+ * per channel ring [P][N+2], W [P][N+2], pw [B+1], E [N+2], G [N+2], prev [B], floats,
+ * channels adjacent.
+ *
+ * crlot_fdaf_create touches no device (CRLOT_EINVAL: a null out, a block no plan
+ * accepts, K < 1 or K > 2^20, channels < 1, a state size or grid that does not fit).
+ * crlot_fdaf_prepare, or the first call that needs the device, makes the internal plan
+ * (frame 2B, hop B) on the current device and allocates and zeroes the state
+ * (crlot_fdaf_state_bytes, valid before prepare; CRLOT_ENOMEM when it does not fit).
+ * A single-owner object like crlot_stream: the hops of one object go on one stream or
+ * are ordered by the caller.  Graph capture is not supported (the hop index is a
+ * by-value kernel argument).  Blocks are channel-major [channels][B], or [B][channels]
+ * after crlot_fdaf_set_layout(af, 1), for x, d, e and y alike.  crlot_fdaf_reset
+ * synchronises the device and zeroes the state (the weights too) and the hop counter.
+ * crlot_fdaf_hop: CRLOT_EINVAL for a null af, d_d or d_e, or when an output block
+ * overlaps an input block or the other output. */
+typedef struct crlot_fdaf crlot_fdaf;
+typedef struct crlot_fdaf_launch {
+    int32_t hop_kernel;        /* CRLOT_K_FDAF_HOP; 0: no hop yet */
+    int32_t update_kernel;     /* CRLOT_K_FDAF_UPDATE; 0: the last hop did not adapt */
+    int32_t constrain_kernel;  /* CRLOT_K_FDAF_CONSTRAIN; 0: mode 0 or not adapting */
+    int32_t reserved;
+    int64_t hop_grid;          /* workgroups: ceil(channels / 4) */
+    int64_t update_grid;       /* workgroups: channels * ceil((B + 1) / 64) */
+    int64_t constrain_grid;    /* workgroups: ceil(channels * partitions constrained / 4) */
+} crlot_fdaf_launch;
+int crlot_fdaf_create(int32_t block, int64_t taps, int32_t channels, crlot_fdaf** out);
+void crlot_fdaf_destroy(crlot_fdaf* af);
+int crlot_fdaf_prepare(crlot_fdaf* af);
+int64_t crlot_fdaf_state_bytes(const crlot_fdaf* af);
+int crlot_fdaf_reset(crlot_fdaf* af);
+int crlot_fdaf_set_layout(crlot_fdaf* af, int32_t interleaved);
+int crlot_fdaf_info(const crlot_fdaf* af, int32_t* channels, int32_t* block, int64_t* taps, int32_t* P,
+                    int64_t* hops);
+int crlot_fdaf_last_launch(const crlot_fdaf* af, crlot_fdaf_launch* out);
+int crlot_fdaf_set_step(crlot_fdaf* af, double mu, double lambda, double delta);
+int crlot_fdaf_set_constraint(crlot_fdaf* af, int32_t mode /* 0 none, 1 round-robin, 2 all */);
+int crlot_fdaf_set_adapt(crlot_fdaf* af, int32_t on /* default 1 */);
+int crlot_fdaf_set_taps(crlot_fdaf* af, const float* h /* host [n_rows][ld] */, int32_t n_rows, int64_t ld);
+int crlot_fdaf_get_taps(crlot_fdaf* af, float* host_out /* [channels][ld] */, int64_t ld);
+int crlot_fdaf_state(crlot_fdaf* af, float** ring, float** W, float** pw, float** E, float** G, float** prev);
+int crlot_fdaf_hop(crlot_fdaf* af, const float* d_x /* NULL: zeros */, const float* d_d, float* d_e,
+                   float* d_y /* may be NULL */, void* stream);
+int crlot_fdaf_constrain(crlot_fdaf* af, int32_t p /* -1: all */, void* stream);
 
 /* host helpers (no device) */
 #define CRLOT_MEL_HTK 0

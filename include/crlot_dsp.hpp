@@ -300,6 +300,85 @@ class StreamConvolver {
     crlot_stream_convolver* s_ = nullptr;
 };
 
+// The partitioned-block frequency-domain adaptive filter (crlot_fdaf_create /
+// crlot_fdaf_hop): per hop B samples of the reference x and of the desired signal d per
+// channel, out the error e = d - y and, when asked, the filter's output y.
+class AdaptiveFilter {
+   public:
+    AdaptiveFilter(int block, int64_t taps, int channels, bool interleaved = false) {
+        check(crlot_fdaf_create(block, taps, channels, &a_), "crlot_fdaf_create");
+        check(crlot_fdaf_set_layout(a_, interleaved ? 1 : 0), "crlot_fdaf_set_layout");
+    }
+    ~AdaptiveFilter() { crlot_fdaf_destroy(a_); }
+    AdaptiveFilter(const AdaptiveFilter&) = delete;
+    AdaptiveFilter& operator=(const AdaptiveFilter&) = delete;
+    AdaptiveFilter(AdaptiveFilter&& o) noexcept : a_(o.a_) { o.a_ = nullptr; }
+    AdaptiveFilter& operator=(AdaptiveFilter&& o) noexcept {
+        if (this != &o) {
+            crlot_fdaf_destroy(a_);
+            a_ = o.a_;
+            o.a_ = nullptr;
+        }
+        return *this;
+    }
+    void prepare() { check(crlot_fdaf_prepare(a_), "crlot_fdaf_prepare"); }
+    void reset() { check(crlot_fdaf_reset(a_), "crlot_fdaf_reset"); }
+    void set_step(double mu, double lambda, double delta) {
+        check(crlot_fdaf_set_step(a_, mu, lambda, delta), "crlot_fdaf_set_step");
+    }
+    // 0: none, 1: round-robin, 2: every partition every hop
+    void set_constraint(int mode) { check(crlot_fdaf_set_constraint(a_, mode), "crlot_fdaf_set_constraint"); }
+    void set_adapt(bool on) { check(crlot_fdaf_set_adapt(a_, on ? 1 : 0), "crlot_fdaf_set_adapt"); }
+    // h: taps() floats per row, one row for every channel or one per channel
+    void set_taps(const float* h, int n_rows, int64_t ld) { check(crlot_fdaf_set_taps(a_, h, n_rows, ld), "crlot_fdaf_set_taps"); }
+    std::vector<float> get_taps() const {
+        const int64_t k = taps();
+        std::vector<float> out(size_t(channels()) * size_t(k));
+        check(crlot_fdaf_get_taps(a_, out.data(), k), "crlot_fdaf_get_taps");
+        return out;
+    }
+    int64_t state_bytes() const {
+        const int64_t n = crlot_fdaf_state_bytes(a_);
+        check(n < 0 ? int(n) : 0, "crlot_fdaf_state_bytes");
+        return n;
+    }
+    int channels() const {
+        int32_t n = 0;
+        check(crlot_fdaf_info(a_, &n, nullptr, nullptr, nullptr, nullptr), "crlot_fdaf_info");
+        return n;
+    }
+    int64_t taps() const {
+        int64_t n = 0;
+        check(crlot_fdaf_info(a_, nullptr, nullptr, &n, nullptr, nullptr), "crlot_fdaf_info");
+        return n;
+    }
+    int partitions() const {
+        int32_t n = 0;
+        check(crlot_fdaf_info(a_, nullptr, nullptr, nullptr, &n, nullptr), "crlot_fdaf_info");
+        return n;
+    }
+    int64_t hops() const {
+        int64_t n = 0;
+        check(crlot_fdaf_info(a_, nullptr, nullptr, nullptr, nullptr, &n), "crlot_fdaf_info");
+        return n;
+    }
+    crlot_fdaf_launch last_launch() const {
+        crlot_fdaf_launch r{};
+        check(crlot_fdaf_last_launch(a_, &r), "crlot_fdaf_last_launch");
+        return r;
+    }
+    // d_x (nullptr: zeros), d_d, d_e, d_y (nullptr: not stored): [channels][block] floats, [block][channels] when interleaved
+    void push_device(const float* d_x, const float* d_d, float* d_e, float* d_y = nullptr, hipStream_t s = nullptr) {
+        check(crlot_fdaf_hop(a_, d_x, d_d, d_e, d_y, s), "crlot_fdaf_hop");
+    }
+    // the gradient constraint alone: partition p of every channel, -1: every partition
+    void constrain(int p = -1, hipStream_t s = nullptr) { check(crlot_fdaf_constrain(a_, p, s), "crlot_fdaf_constrain"); }
+    crlot_fdaf* get() const { return a_; }
+
+   private:
+    crlot_fdaf* a_ = nullptr;
+};
+
 // Batched round trip: n_streams mono streams, each T samples.
 class StftEngine {
    public:
