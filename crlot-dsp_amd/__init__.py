@@ -139,6 +139,18 @@ class FdafLaunch(C.Structure):
                 ("constrain_grid", C.c_int64)]
 
 
+class DenoiseDesc(C.Structure):
+    """crlot_denoise_desc (include/crlot_dsp.h)."""
+    _fields_ = [("alpha_s", C.c_double), ("alpha_p", C.c_double), ("alpha_d", C.c_double), ("delta", C.c_double),
+                ("alpha_dd", C.c_double), ("g_min", C.c_double), ("window", C.c_int32), ("reserved", C.c_int32)]
+
+
+class DenoiseLaunch(C.Structure):
+    """crlot_denoise_launch (include/crlot_dsp.h): what a noise suppressor's last call launched."""
+    _fields_ = [("route", C.c_int32), ("n_kernels", C.c_int32), ("kernel", C.c_int32 * 3), ("reserved", C.c_int32),
+                ("grid", C.c_int64 * 3)]
+
+
 class FftDesc(C.Structure):
     """crlot_fft_desc (include/crlot_dsp.h)."""
     _fields_ = [("domain", C.c_int32), ("nfft", C.c_int32), ("device", C.c_int32)]
@@ -245,6 +257,19 @@ def lib():
         "crlot_fdaf_state": ([vp] + [C.POINTER(vp)] * 6, C.c_int),
         "crlot_fdaf_hop": ([vp, vp, vp, vp, vp, vp], C.c_int),
         "crlot_fdaf_constrain": ([vp, i32, vp], C.c_int),
+        "crlot_denoise_desc_default": ([C.POINTER(DenoiseDesc)], C.c_int),
+        "crlot_denoiser_create": ([vp, C.POINTER(DenoiseDesc), i32, C.POINTER(vp)], C.c_int),
+        "crlot_denoiser_destroy": ([vp], None),
+        "crlot_denoiser_prepare": ([vp], C.c_int),
+        "crlot_denoiser_reset": ([vp], C.c_int),
+        "crlot_denoiser_info": ([vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i64), C.POINTER(i32), C.POINTER(i32)],
+                                C.c_int),
+        "crlot_denoiser_state": ([vp, C.POINTER(vp)], C.c_int),
+        "crlot_denoiser_set_route": ([vp, i32], C.c_int),
+        "crlot_denoiser_last_launch": ([vp, C.POINTER(DenoiseLaunch)], C.c_int),
+        "crlot_denoise_gains": ([vp, vp, vp, i32, i64, i64, i64, i64, i64, i32, vp], C.c_int),
+        "crlot_denoise": ([vp, vp, vp, i32, i64, i64, i64, vp], C.c_int),
+        "crlot_stream_denoise_hop": ([vp, vp, vp, vp, C.POINTER(i32), vp], C.c_int),
         "crlot_resample_geometry": ([C.POINTER(ResamplerDesc), C.POINTER(ResamplerGeometry)], C.c_int),
         "crlot_resample_table_host": ([C.POINTER(ResamplerDesc), fp], C.c_int),
         "crlot_rational_approx": ([C.c_double, i32, C.POINTER(i32), C.POINTER(i32)], C.c_int),
@@ -1854,6 +1879,138 @@ class AdaptiveFilter:
         _check(lib().crlot_fdaf_constrain(self._h, int(p), stream), "crlot_fdaf_constrain")
 
 
+# ----------------------------------------------------------------- noise suppressor
+DENOISE_DEFAULTS = dict(alpha_s=0.8, alpha_p=0.2, alpha_d=0.95, delta=5.0, window=64, alpha_dd=0.98, g_min=0.1)
+DENOISE_PLANES = ("S", "Smin", "Stmp", "p", "lam", "A2")
+
+
+def denoise_desc(**kw) -> DenoiseDesc:
+    """A crlot_denoise_desc from DENOISE_DEFAULTS and the overrides given."""
+    unknown = set(kw) - set(DENOISE_DEFAULTS)
+    if unknown:
+        raise ValueError(f"unknown denoise parameters: {sorted(unknown)}")
+    v = {**DENOISE_DEFAULTS, **kw}
+    return DenoiseDesc(float(v["alpha_s"]), float(v["alpha_p"]), float(v["alpha_d"]), float(v["delta"]),
+                       float(v["alpha_dd"]), float(v["g_min"]), int(v["window"]), 0)
+
+
+class Denoiser:
+    """The stationary-noise suppressor (crlot_denoiser_create; MCRA noise tracking and a
+    decision-directed Wiener gain): gains(spec) gives the mask rows of a spectrogram,
+    denoise(x) is stft -> gains -> masked istft_ola in one call, and Stream.denoise_hop
+    runs it per hop with the state carried in this object.  Creation checks the
+    parameters (ValueError) and touches no device."""
+
+    def __init__(self, plan: "Plan", channels: int, **params):
+        self._h = None
+        self.plan, self.channels = plan, int(channels)
+        self.bins = plan.frame_size // 2 + 1
+        desc = denoise_desc(**params)
+        h = C.c_void_p()
+        _check(lib().crlot_denoiser_create(plan._h, C.byref(desc), int(channels), C.byref(h)), "crlot_denoiser_create")
+        self._h = h
+        self.params = {k: getattr(desc, k) for k in DENOISE_DEFAULTS}
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().crlot_denoiser_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # interpreter shutdown
+            pass
+
+    def _info(self):
+        ch, bins, route, ok = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        frames = C.c_int64()
+        _check(lib().crlot_denoiser_info(self._h, C.byref(ch), C.byref(bins), C.byref(frames), C.byref(route),
+                                         C.byref(ok)), "crlot_denoiser_info")
+        return {"channels": ch.value, "bins": bins.value, "frames": frames.value, "route": route.value,
+                "fused_ok": bool(ok.value)}
+
+    @property
+    def frames(self) -> int:
+        """Frames the carried state has seen since create / reset."""
+        return self._info()["frames"]
+
+    @property
+    def fused_ok(self) -> bool:
+        return self._info()["fused_ok"]
+
+    def prepare(self):
+        with _torch().cuda.device(self.plan._device_index()):
+            _check(lib().crlot_denoiser_prepare(self._h), "crlot_denoiser_prepare")
+
+    def reset(self):
+        """Zero the state and the frame counter."""
+        _check(lib().crlot_denoiser_reset(self._h), "crlot_denoiser_reset")
+
+    def set_route(self, route: int = 0):
+        """The per-hop route: 0 the library's choice, 1 fused (one launch), 2 staged (three)."""
+        _check(lib().crlot_denoiser_set_route(self._h, int(route)), "crlot_denoiser_set_route")
+
+    def state(self):
+        """The carried state on the device, a (channels, 6, N/2+1) float32 torch view in
+        DENOISE_PLANES order (valid while this object lives, zeroed by reset)."""
+        torch = _torch()
+        ptr = C.c_void_p()
+        dev = self.plan._device_index()
+        with torch.cuda.device(dev):
+            _check(lib().crlot_denoiser_state(self._h, C.byref(ptr)), "crlot_denoiser_state")
+            return torch.as_tensor(_DeviceFloats(ptr.value, (self.channels, 6, self.bins)), device=f"cuda:{dev}")
+
+    def last_launch(self) -> dict:
+        r = DenoiseLaunch()
+        _check(lib().crlot_denoiser_last_launch(self._h, C.byref(r)), "crlot_denoiser_last_launch")
+        kernels = [int(r.kernel[i]) for i in range(r.n_kernels)]
+        return {"route": r.route, "kernels": kernels, "names": [kernel_name(k) for k in kernels],
+                "grids": [int(r.grid[i]) for i in range(r.n_kernels)]}
+
+    def gains(self, spec, mask=None, carry: bool = False, stream: int | None = None):
+        """spec: (S, F, N/2+1) or (F, N/2+1) complex64 device tensor -> the gain rows, float32
+        of the same shape (what Plan.set_spectral_mask takes).  carry=False: every stream
+        starts at frame 0 and the object's state is left alone; carry=True: S must be the
+        channel count, the run continues from the object's state and advances it."""
+        torch = _torch()
+        if len(spec.shape) == 2:
+            return self.gains(spec[None], None if mask is None else mask[None], carry, stream)[0]
+        dev = self.plan._device_index()
+        ld_s, ldf_s = _stretch_spec_layout(*_tensor_layout(spec), dev, self.bins)
+        S, F = int(spec.shape[0]), int(spec.shape[1])
+        if carry and S != self.channels:
+            raise ValueError(f"carry needs {self.channels} streams, not {S}")
+        if mask is None:
+            mask = torch.empty((S, F, self.bins), dtype=torch.float32, device=spec.device)
+        _, _, ld_m, ldf_m = _gl_mag_layout(*_tensor_layout(mask), dev, self.bins, "mask", (S, F, self.bins))
+        if _tensors_overlap(mask, spec):
+            raise ValueError("mask overlaps spec")
+        s = _stream_handle(spec) if stream is None else stream
+        _check(lib().crlot_denoise_gains(self._h, spec.data_ptr(), mask.data_ptr(), S, F, ld_s, ldf_s, ld_m, ldf_m,
+                                         int(bool(carry)), s), "crlot_denoise_gains")
+        return mask
+
+    def denoise(self, x, y=None, stream: int | None = None):
+        """x: (S, T) or (T,) float32 device tensor -> y: (S, F * H), istft_ola of stft(x) under
+        gains(stft(x)), bit for bit, with the spectra and the gains in the plan's scratch.
+        The plan must have no stored spectral mask."""
+        if x.dim() == 1:
+            return self.denoise(x[None], None if y is None else y[None], stream)[0]
+        S, T = _spectrogram_x_layout(*_tensor_layout(x))
+        if getattr(self.plan, "_mask", None) is not None:
+            raise ValueError("denoise: the plan has a stored spectral mask; clear it first")
+        L = self.plan.frame_count(T) * self.plan.hop_size
+        if y is None:
+            y = _torch().empty((S, L), dtype=x.dtype, device=x.device)
+        ld_y = _gl_y_layout(*_tensor_layout(y), self.plan._device_index(), S, L)
+        if _tensors_overlap(y, x):
+            raise ValueError("y overlaps x")
+        s = _stream_handle(x) if stream is None else stream
+        _check(lib().crlot_denoise(self._h, x.data_ptr(), y.data_ptr(), S, T, _ld(x, 0, T), ld_y, s), "crlot_denoise")
+        return y
+
+
 class FftPlan:
     """dsp::fft::IFftPlan on the device (fft_api.h:26-48), both domains.
 
@@ -2249,6 +2406,28 @@ class Stream:
         s = _stream_handle(hop) if stream is None else stream
         _check(lib().crlot_stream_push_hop_masked(self._h, hop.data_ptr(), mp, ldm, out.data_ptr(), C.byref(em), s),
                "crlot_stream_push_hop_masked")
+        return out, em.value
+
+
+    def denoise_hop(self, denoiser, hop, out=None, stream: int | None = None) -> tuple:
+        """push_hop with the noise suppressor's gain row of the frame this hop completes
+        (crlot_stream_denoise_hop); denoiser: a Denoiser of this stream's plan and channel
+        count, whose state the hop advances.  Returns (out, emitted), emitted 0 or H."""
+        torch = _torch()
+        hop = self._hop_arg(hop)
+        if not isinstance(denoiser, Denoiser):
+            raise ValueError("denoiser must be a Denoiser object")
+        if denoiser.plan is not self.plan:
+            raise ValueError("the denoiser was created on another plan")
+        if denoiser.channels != self.channels:
+            raise ValueError(f"the denoiser has {denoiser.channels} channels, the stream {self.channels}")
+        if out is None:
+            out = torch.empty_like(hop)
+        self._hop_arg(out, "out")
+        em = C.c_int32()
+        s = _stream_handle(hop) if stream is None else stream
+        _check(lib().crlot_stream_denoise_hop(self._h, denoiser._h, hop.data_ptr(), out.data_ptr(), C.byref(em), s),
+               "crlot_stream_denoise_hop")
         return out, em.value
 
 

@@ -464,15 +464,23 @@ __device__ __forceinline__ cf dc_merge(cf x0, cf xp) { return {x0.r + xp.r, x0.r
 // left as it came: a forward transform that only writes its spectrum).
 // sink (optional): called as sink(m, xk, xpk) with the step's X[k], X[P-k] of
 // k = lane + 64 m, in m order, for a caller that keeps the spectrum in registers.
+// step (optional): called as step(m, xk, xpk, gk, gpk) with X[k], X[P-k] BEFORE the gain,
+// in m order; the real multipliers it returns in gk, gpk multiply re and im of X[k] and
+// X[P-k] after the gain and the mask (the step is ((X * gain) * mask) * g): a gain the
+// kernel computes from the spectrum itself, where a mask row would be read.
 struct NoBinSink {
     __device__ __forceinline__ void operator()(int, const cf&, const cf&) const {}
 };
-template <int E, bool HAS_GAIN, bool WRITE_SPEC, bool HAS_MASK = false, bool MERGE = true, typename SINK = NoBinSink>
+struct NoBinStep {
+    __device__ __forceinline__ void operator()(int, const cf&, const cf&, float&, float&) const {}
+};
+template <int E, bool HAS_GAIN, bool WRITE_SPEC, bool HAS_MASK = false, bool MERGE = true, typename SINK = NoBinSink,
+          typename STEP = NoBinStep>
 __device__ __forceinline__ void real_split_hook_merge(cf (&v)[E], cf* buf, const cf* st,
                                                       const cf* sth, const float* gain,
                                                       int lane, cf* spec = nullptr,
                                                       const float* mk = nullptr, const float* mpk = nullptr,
-                                                      SINK sink = SINK()) {
+                                                      SINK sink = SINK(), STEP step = STEP()) {
     constexpr int P = 64 * E;
 #pragma unroll
     for (int m = 0; m < E; ++m) buf[lane + 64 * m] = v[m];  // conflict free unswizzled
@@ -496,6 +504,8 @@ __device__ __forceinline__ void real_split_hook_merge(cf (&v)[E], cf* buf, const
         cf xk = {__builtin_fmaf(f1.r, 0.5f, t.r), __builtin_fmaf(f1.i, 0.5f, t.i)};
         cf xpk = {__builtin_fmaf(f1.r, 0.5f, -t.r), __builtin_fmaf(f1.i, -0.5f, t.i)};  // X[P-k]
         if (m == 0 && lane == 0) dc_split(zk, xk, xpk);
+        [[maybe_unused]] float sk = 1.0f, spk = 1.0f;
+        if constexpr (!std::is_same_v<STEP, NoBinStep>) step(m, xk, xpk, sk, spk);
         if constexpr (HAS_GAIN) {
             const float gk = gain[k], gpk = gain[P - k];
             xk = {xk.r * gk, xk.i * gk};
@@ -504,6 +514,10 @@ __device__ __forceinline__ void real_split_hook_merge(cf (&v)[E], cf* buf, const
         if constexpr (HAS_MASK) {
             xk = {xk.r * mk[m], xk.i * mk[m]};
             xpk = {xpk.r * mpk[m], xpk.i * mpk[m]};
+        }
+        if constexpr (!std::is_same_v<STEP, NoBinStep>) {
+            xk = {xk.r * sk, xk.i * sk};
+            xpk = {xpk.r * spk, xpk.i * spk};
         }
         if constexpr (WRITE_SPEC) {
             spec[k] = xk;

@@ -9,6 +9,7 @@
 
 #include "ab.h"
 #include "crlot_dsp.h"
+#include "denoise_chain.h"
 
 namespace crlot {
 
@@ -703,6 +704,21 @@ struct FdafArgs {
 hipError_t launch_fdaf_hop(const FdafArgs& a, int64_t* grid, hipStream_t s);
 hipError_t launch_fdaf_update(const FdafArgs& a, int64_t* grid, hipStream_t s);
 hipError_t launch_fdaf_constrain(const FdafArgs& a, int64_t* grid, hipStream_t s);
+
+// ---- denoise.hip: the noise suppressor's gains (crlot_denoise_gains; the contract is in include/crlot_dsp.h)
+// K_denoise_gains over a.F frames of a.n_streams streams (denoise_chain.h GainsArgs), one
+// wave per 64 adjacent bins of a stream.  record: list it in the call's launch record.
+// *grid: workgroups launched.  hipErrorInvalidValue: a bad argument or a grid beyond 2^31-1.
+hipError_t launch_denoise_gains(const denoise::GainsArgs& a, bool record, int64_t* grid, hipStream_t s);
+// ... and launch_stream_hop with the suppressor's gain of the frame the hop
+// completes (k >= 0; k < 0: none, the state is not touched) in the mask row's place, the
+// state block [channels][6][N/2+1] advanced in the same launch (k_stream_denoise:
+// fused shapes with N <= 1024)
+bool stream_denoise_fused_supported(int n, int h);
+hipError_t launch_stream_denoise_hop(const Geometry& g, const DevTables& t, const float* in, int64_t in_ld,
+                                     int64_t in_inc, float* out, int64_t out_ld, int64_t out_inc, float* hist,
+                                     float* acc, int channels, int64_t q, float* state, const denoise::Params& prm,
+                                     int64_t k, hipStream_t stream);
 
 // dsp::FrameQueue frames on the device: [stream][F][N] from x [stream][ld_x]
 hipError_t launch_fq_frames(const float* x, int64_t T, int64_t ld_x, int n_streams, float* frames, int64_t F,

@@ -189,6 +189,10 @@ extern "C" const char* crlot_kernel_name(int32_t id) {
         case CRLOT_K_FDAF_HOP: return "k_fdaf_hop";
         case CRLOT_K_FDAF_UPDATE: return "k_fdaf_update";
         case CRLOT_K_FDAF_CONSTRAIN: return "k_fdaf_constrain";
+        case CRLOT_K_DENOISE_GAINS: return "k_denoise_gains";
+        case CRLOT_K_DENOISE_HOP: return "k_stream_denoise";
+        case CRLOT_K_STREAM_STFT: return "k_stream_stft";
+        case CRLOT_K_STREAM_ISTFT: return "k_stream_istft";
         case CRLOT_K_EXPERIMENT: return "k_experiment";
         default: return "unknown";
     }

@@ -99,7 +99,25 @@ struct crlot_features {
     float* d_w = nullptr;                // the spans' weights, band after band
 };
 
+// The noise suppressor (denoise_host.cpp); the streaming hop (stream_host.cpp) reads it too.
+struct crlot_denoiser {
+    crlot_plan* plan = nullptr;
+    int device = 0;
+    int32_t channels = 0, bins = 0;
+    crlot::denoise::Params q{};
+    int route = 0;        // crlot_denoiser_set_route
+    int64_t frames = 0;   // frames the carried state has seen
+    crlot_denoise_launch last{};
+    // filled by prepare: one allocation [state C 6 bins][spectrum rows C (N+2)][mask rows C bins]
+    float* d_state = nullptr;
+    float* d_spec = nullptr;
+    float* d_mask = nullptr;
+};
+
 namespace crlot {
+
+// denoise_host.cpp: allocate and zero the suppressor's device block once
+int denoiser_ensure_state(crlot_denoiser* dn);
 
 // ------------------------------------------------------------------ errors
 // crlot_last_error()'s thread-local slot is in abi.cpp; every setter returns `code`.

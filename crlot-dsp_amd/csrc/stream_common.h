@@ -8,6 +8,7 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "denoise_chain.h"
 #include "feat_common.h"
 #include "fft_any.h"
 #include "fft_wave.h"
@@ -172,7 +173,20 @@ struct HopSpec {
 // kHopFeat: kHopStft up to and including the split; the spectrum stays in registers
 //   and its features (FeatDev: feat_common.h's per-bin value, band stage and log) go
 //   to channel c's row fd.out + c fd.ld_out; g.spec non-null: kHopStft's row as well.
-enum : int { kHopWhole = 0, kHopStft = 1, kHopIstft = 2, kHopFeat = 3 };
+// kHopDenoise: kHopWhole with the noise suppressor's gain (denoise_chain.h) as the frame's
+//   mask row: the six state planes of the lane's bins k and P - k (lane 0's P - k is bin P,
+//   as a mask row is laid out) are read where the mask row would be, advanced between split
+//   and merge from X before the gain, and stored back after the merge.  Bin k is stored by
+//   the lane that holds it as X[k] (bin P by lane 0), the value kHopStft stores for it.
+enum : int { kHopWhole = 0, kHopStft = 1, kHopIstft = 2, kHopFeat = 3, kHopDenoise = 4 };
+// What kHopDenoise adds to a hop's arguments: the state block [channels][6][P + 1] and the
+// frame's place in the recurrence (the same for every channel of the launch).
+struct DenoiseHop {
+    float* state = nullptr;
+    denoise::Params q{};
+    int32_t first = 0;  // the frame this hop completes is frame 0
+    int32_t wrap = 0;   // its index is a multiple of the window
+};
 
 // One hop of the low-latency path (BASELINE config 4): per channel, the last
 // NB = N/H hops live in `hist` (slot q mod NB holds hop q) and the OLA
@@ -183,10 +197,12 @@ enum : int { kHopWhole = 0, kHopStft = 1, kHopIstft = 2, kHopFeat = 3 };
 // The lane that owns frame sample i owns it in every frame (H % 128 == 0), so a
 // lane only ever touches its own acc words: no cross-lane hazards.
 template <int E, int S, int MODE, bool HAS_GAIN, bool HAS_MASK>
-__device__ __forceinline__ void stream_hop_body(const StreamArgs& a, const HopSpec& g, const FeatDev& fd = FeatDev{}) {
+__device__ __forceinline__ void stream_hop_body(const StreamArgs& a, const HopSpec& g, const FeatDev& fd = FeatDev{},
+                                                const DenoiseHop& dn = DenoiseHop{}) {
     constexpr int P = 64 * E, N = 2 * P, H = 128 * S, NB = E / S;
-    constexpr bool IN = MODE != kHopIstft;                       // consumes a hop (hist)
-    constexpr bool OUT = MODE == kHopWhole || MODE == kHopIstft;  // produces a block (acc)
+    constexpr bool DN = MODE == kHopDenoise;
+    constexpr bool IN = MODE != kHopIstft;                             // consumes a hop (hist)
+    constexpr bool OUT = MODE == kHopWhole || MODE == kHopIstft || DN;  // produces a block (acc)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     cf* tw = reinterpret_cast<cf*>(smem);
     cf* st = tw + P;
@@ -211,6 +227,7 @@ __device__ __forceinline__ void stream_hop_body(const StreamArgs& a, const HopSp
     float2 xps[IN ? 1 : E];    // istft: X[P-k] (m = 0 of lane 0: X[P]), a reversed coalesced row
     float mk[HAS_MASK ? E : 1], mpk[HAS_MASK ? E : 1];  // mask[k], mask[P-k]
     float gk[(!IN && HAS_GAIN) ? E : 1], gpk[(!IN && HAS_GAIN) ? E : 1];
+    denoise::State sk[DN ? E : 1], spk[DN ? E : 1];  // the suppressor's state of bins k, P - k
     float2 cur[OUT ? E : 1];   // OLA blocks this frame adds to
     float2 dd[OUT ? S : 1];    // divisors of the block that completes
     if constexpr (IN) {
@@ -243,6 +260,24 @@ __device__ __forceinline__ void stream_hop_body(const StreamArgs& a, const HopSp
             const int k = lane + 64 * m;
             mk[m] = frame ? mr[k] : 1.0f;
             mpk[m] = frame ? mr[P - k] : 1.0f;
+        }
+    }
+    // kHopDenoise: the state planes in the mask row's place, for the same reason; frame 0
+    // starts every column afresh and reads nothing
+    if constexpr (DN) {
+        const float* sr = dn.state + int64_t(cc) * (denoise::kPlanes * (P + 1));
+        const bool rd = frame && !dn.first;
+#pragma unroll
+        for (int m = 0; m < E; ++m) {
+            const int k = lane + 64 * m;
+            const float* a0 = sr + k;
+            const float* a1 = sr + (P - k);
+            sk[m] = rd ? denoise::State{a0[0], a0[P + 1], a0[2 * (P + 1)], a0[3 * (P + 1)], a0[4 * (P + 1)],
+                                        a0[5 * (P + 1)]}
+                       : denoise::State{0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            spk[m] = rd ? denoise::State{a1[0], a1[P + 1], a1[2 * (P + 1)], a1[3 * (P + 1)], a1[4 * (P + 1)],
+                                         a1[5 * (P + 1)]}
+                        : denoise::State{0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         }
     }
 #pragma unroll
@@ -279,6 +314,16 @@ __device__ __forceinline__ void stream_hop_body(const StreamArgs& a, const HopSp
         load_tables<E>(a.t, tw, st, sth, wa, ws, true, nullptr, [&]() {
 #pragma unroll
             for (int m = 0; m < E; ++m) asm volatile("" : "+v"(mk[m]), "+v"(mpk[m]));
+        });
+    } else if constexpr (DN) {
+        load_tables<E>(a.t, tw, st, sth, wa, ws, true, nullptr, [&]() {
+#pragma unroll
+            for (int m = 0; m < E; ++m) {
+                asm volatile("" : "+v"(sk[m].S), "+v"(sk[m].Smin), "+v"(sk[m].Stmp), "+v"(sk[m].p), "+v"(sk[m].lam),
+                             "+v"(sk[m].A2));
+                asm volatile("" : "+v"(spk[m].S), "+v"(spk[m].Smin), "+v"(spk[m].Stmp), "+v"(spk[m].p),
+                             "+v"(spk[m].lam), "+v"(spk[m].A2));
+            }
         });
     } else {
         load_tables<E>(a.t, tw, st, sth, wa, ws, true);
@@ -336,6 +381,37 @@ __device__ __forceinline__ void stream_hop_body(const StreamArgs& a, const HopSp
                     } else {
                         dev::feat_bands<1>(fd, fd.bands, fd.w, vals, 0, rows, lane);
                     }
+                }
+            } else if constexpr (DN) {
+                // each bin's step from X before the gain; bin P / 2 (k == P - k) is held twice by
+                // its lane: it advances once, as X[k], and that G multiplies both copies
+                const bool first = dn.first != 0, wrap = dn.wrap != 0;
+                dev::real_split_hook_merge<E, HAS_GAIN, false, false, true>(
+                    v, buf, st, sth, a.t.gain, lane, nullptr, nullptr, nullptr, dev::NoBinSink(),
+                    [&](int m, const cf& xk, const cf& xpk, float& gk, float& gpk) __attribute__((always_inline)) {
+                        gk = denoise::step(sk[m], xk.r, xk.i, first, wrap, dn.q);
+                        const float gp = denoise::step(spk[m], xpk.r, xpk.i, first, wrap, dn.q);
+                        gpk = 2 * (lane + 64 * m) == P ? gk : gp;
+                    });
+                float* sr = dn.state + int64_t(c) * (denoise::kPlanes * (P + 1));
+#pragma unroll
+                for (int m = 0; m < E; ++m) {
+                    float* o = sr + lane + 64 * m;
+                    o[0] = sk[m].S;
+                    o[P + 1] = sk[m].Smin;
+                    o[2 * (P + 1)] = sk[m].Stmp;
+                    o[3 * (P + 1)] = sk[m].p;
+                    o[4 * (P + 1)] = sk[m].lam;
+                    o[5 * (P + 1)] = sk[m].A2;
+                }
+                if (lane == 0) {
+                    float* o = sr + P;
+                    o[0] = spk[0].S;
+                    o[P + 1] = spk[0].Smin;
+                    o[2 * (P + 1)] = spk[0].Stmp;
+                    o[3 * (P + 1)] = spk[0].p;
+                    o[4 * (P + 1)] = spk[0].lam;
+                    o[5 * (P + 1)] = spk[0].A2;
                 }
             } else {
                 dev::real_split_hook_merge<E, HAS_GAIN, false, HAS_MASK>(v, buf, st, sth, a.t.gain, lane, nullptr, mk,

@@ -252,6 +252,81 @@ int crlot_stream_istft_hop(crlot_stream* st, const float* d_spec, int64_t ld_spe
     return CRLOT_OK;
 }
 
+// push_hop with the noise suppressor's gain row of the frame the hop completes (the
+// contract is in include/crlot_dsp.h, "noise suppressor").  Fused: one launch, the state
+// advanced inside it.  Staged: the analysis half into the object's spectrum rows, the
+// gains kernel with F = 1 on the object's state, the synthesis half with the gains as
+// its mask row -- the whole-mode hop's state layout is the split halves'.
+int crlot_stream_denoise_hop(crlot_stream* st, crlot_denoiser* dn, const float* d_in, float* d_out, int32_t* emitted,
+                             void* stream) {
+    if (emitted) *emitted = 0;
+    if (!st) return fail(CRLOT_EINVAL, "null stream");
+    if (!dn) return fail(CRLOT_EINVAL, "null noise suppressor");
+    if (!d_in || !d_out) return fail(CRLOT_EINVAL, "null buffer");
+    if (dn->plan != st->plan) return fail(CRLOT_EINVAL, "the noise suppressor was created on another plan");
+    if (dn->channels != st->channels)
+        return fail(CRLOT_EINVAL, "the noise suppressor's channel count differs from the stream's");
+    crlot_plan* p = st->plan;
+    const int64_t C = st->channels, H = p->geo.h;
+    if (dn->frames != drop_frames_after(st->q, p->geo.n, H))
+        return fail(CRLOT_ERUNTIME, "the noise suppressor's frame counter differs from the stream's; reset both");
+    if (int rc = stream_enter(st, 1)) return rc;
+    if (int rc = denoiser_ensure_state(dn)) return rc;
+    DeviceGuard g(p->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int64_t ld = st->interleaved ? 1 : H, inc = st->interleaved ? C : 1;
+    const int64_t k = stream_frame_of_hop(st, st->q);
+    const bool fused = dn->route != 2 && !st->any && crlot::stream_denoise_fused_supported(p->geo.n, p->geo.h);
+    if (dn->route == 1 && !fused) return fail(CRLOT_EUNSUPPORTED, "the fused denoise hop has no instantiation at this shape");
+    crlot_denoise_launch rec{};
+    const int64_t hop_grid = st->any ? 0 : (C + 3) / 4;  // (the mixed-radix kernels size their own workgroups)
+    hipError_t e;
+    if (fused) {
+        e = crlot::launch_stream_denoise_hop(p->geo, tables(p), d_in, ld, inc, d_out, ld, inc, st->d_hist, st->d_acc,
+                                             st->channels, st->q, dn->d_state, dn->q, k, s);
+        if (e != hipSuccess) return hip_fail(e, "stream kernel launch");
+        rec.route = 1;
+        rec.n_kernels = 1;
+        rec.kernel[0] = CRLOT_K_DENOISE_HOP;
+        rec.grid[0] = hop_grid;
+    } else {
+        const int64_t row = int64_t(p->geo.n) + 2, bins = dn->bins;
+        e = crlot::launch_stream_stft_hop(p->geo, tables(p), p->d_twany, st->any, d_in, ld, inc, dn->d_spec, row,
+                                          st->d_hist, st->channels, st->q, k, s);
+        if (e != hipSuccess) return hip_fail(e, "stream kernel launch");
+        rec.route = 2;
+        rec.n_kernels = 1;
+        rec.kernel[0] = CRLOT_K_STREAM_STFT;
+        rec.grid[0] = hop_grid;
+        if (k >= 0) {
+            crlot::denoise::GainsArgs a{};
+            a.spec = dn->d_spec;
+            a.mask = dn->d_mask;
+            a.state_in = a.state_out = dn->d_state;
+            a.ld_spec = row, a.ldf_spec = row, a.ld_mask = bins, a.ldf_mask = bins;
+            a.F = 1;
+            a.k0 = k;
+            a.n_streams = st->channels;
+            a.bins = int32_t(bins);
+            a.q = dn->q;
+            if ((e = crlot::launch_denoise_gains(a, false, &rec.grid[1], s)) != hipSuccess)
+                return hip_fail(e, "denoise gains launch");
+            e = crlot::launch_stream_istft_hop(p->geo, tables(p), p->d_twany, st->any, dn->d_spec, row, dn->d_mask,
+                                               bins, d_out, ld, inc, st->d_acc, st->channels, k, s);
+            if (e != hipSuccess) return hip_fail(e, "stream kernel launch");
+            rec.n_kernels = 3;
+            rec.kernel[1] = CRLOT_K_DENOISE_GAINS;
+            rec.kernel[2] = CRLOT_K_STREAM_ISTFT;
+            rec.grid[2] = hop_grid;
+        }
+    }
+    dn->last = rec;
+    if (k >= 0) dn->frames += 1;
+    if (emitted) *emitted = k >= 0 ? int32_t(H) : 0;
+    st->q += 1;
+    return CRLOT_OK;
+}
+
 }  // extern "C"
 
 // ------------------------------------------------------------------ resident streaming

@@ -271,6 +271,11 @@ int crlot_test_inject(int32_t what, int32_t count);
 #define CRLOT_K_FDAF_HOP 49     /* crlot_fdaf_hop: filter, error, power estimate, error spectrum and gradient */
 #define CRLOT_K_FDAF_UPDATE 50  /* ... the weight update over the partitions */
 #define CRLOT_K_FDAF_CONSTRAIN 51 /* ... the gradient constraint (crlot_fdaf_constrain) */
+/* (52 is not assigned: crlot_kernel_name(52) stays "unknown") */
+#define CRLOT_K_DENOISE_GAINS 53 /* crlot_denoise_gains: the suppressor's gains over spectra in HBM, a lane per column */
+#define CRLOT_K_DENOISE_HOP 54  /* crlot_stream_denoise_hop, fused: the hop with the gain computed in the mask row's place */
+#define CRLOT_K_STREAM_STFT 55  /* ... staged: the hop's analysis half (crlot_stream_stft_hop's kernel) */
+#define CRLOT_K_STREAM_ISTFT 56 /* ... staged: the synthesis half with the gains as its mask row */
 #define CRLOT_K_EXPERIMENT 99   /* experiment builds only */
 typedef struct crlot_launch_info {
     int32_t n_kernels;
@@ -1125,6 +1130,125 @@ int crlot_fdaf_state(crlot_fdaf* af, float** ring, float** W, float** pw, float*
 int crlot_fdaf_hop(crlot_fdaf* af, const float* d_x /* NULL: zeros */, const float* d_d, float* d_e,
                    float* d_y /* may be NULL */, void* stream);
 int crlot_fdaf_constrain(crlot_fdaf* af, int32_t p /* -1: all */, void* stream);
+
+/* ---------------------------------------------------------------- noise suppressor
+ * A stationary-noise suppressor on the spectral step: MCRA noise tracking (Cohen &
+ * Berdugo 2002, without its smoothing along frequency) and a decision-directed Wiener
+ * gain (Ephraim & Malah 1984).  Per (channel, bin b <= N/2) six float32 state values --
+ * S, Smin, Stmp, p, lam, A2 -- are carried from frame to frame; frame k's gain row G
+ * [N/2+1] is what crlot_plan_set_spectral_mask / crlot_stream_push_hop_masked take as a
+ * mask row.  Offline: crlot_denoise_gains (spectra -> mask rows) and crlot_denoise
+ * (x -> y).  Per hop: crlot_stream_denoise_hop, the state inside the hop's launch.
+ *
+ * Values.  float32, every product, sum and quotient rounded on its own (no FMA), the
+ * division correctly rounded; min(a, b) is a < b ? a : b and max(a, b) is a > b ? a : b.
+ * Each factor alpha_* of the descriptor is rounded to float32 and its complement is
+ * omega_* = float32(1 - alpha_*), formed in double.  X is the row crlot_stft /
+ * crlot_stream_stft_hop stores for the frame: before the plan gain, the DC and Nyquist
+ * imaginary parts 0.  Per bin and frame k, counted from create / reset (or k0 + row):
+ *   1  P = (Xr Xr) + (Xi Xi);
+ *   2  k = 0: S = Smin = Stmp = lam = P, p = 0, A2 = 0;
+ *   3  k > 0: S = (alpha_s S) + (omega_s P);
+ *      k mod window == 0: Smin = min(Stmp, S), Stmp = S;
+ *      otherwise:         Smin = min(Smin, S), Stmp = min(Stmp, S);
+ *      I = S > (delta Smin);  p = (alpha_p p) + (I ? omega_p : 0);
+ *      ad = alpha_d + (omega_d p);  lam = (ad lam) + ((1 - ad) P);
+ *   4  lc = max(lam, 1e-30f); gamma = P / lc;
+ *      xi = (alpha_dd (A2 / lc)) + (omega_dd max(gamma - 1, 0));
+ *   5  G = max(xi / (1 + xi), g_min);  A2 = (G G) P;
+ *   6  the step on the frame is ((X gain) G) on re and im each: a mask row G.
+ * Output bits do not depend on the grid, the stream count, the leading dimensions, a
+ * channel's position, or where a run is cut: the gains of F frames equal the gains of F1
+ * frames followed by those of F - F1 with the state carried.
+ *
+ * Descriptor (crlot_denoise_desc_default fills the defaults): alpha_s 0.8, alpha_p 0.2,
+ * alpha_d 0.95, alpha_dd 0.98, each in [0, 1); delta 5 (> 0); window 64 frames (>= 1);
+ * g_min 0.1 in [0, 1].  It is checked before any device work: a value outside its range
+ * or not finite is CRLOT_EINVAL.
+ *
+ * crlot_denoiser_create(plan, desc, channels, out) touches no device (CRLOT_EINVAL: a null
+ * argument, a bad descriptor, channels < 1, a state size or grid that does not fit).  prepare, or
+ * the first call that needs it, allocates the state block [channels][6][N/2+1] (planes in
+ * the order above), one spectrum row and one mask row per channel (the staged hop's), zeroed.
+ * crlot_denoiser_state returns the state block's device pointer; crlot_denoiser_reset
+ * synchronises the device, zeroes the block and the frame counter.  A single-owner object
+ * like crlot_stream; graph capture is not supported (the frame index is by value).
+ *
+ * crlot_denoise_gains(dn, d_spec, d_mask, n_streams, F, ld_spec, ldf_spec, ld_mask, ldf_mask,
+ * carry, stream): spectra in crlot_stft's layout (frame f of stream s at d_spec + s ld_spec
+ * + f ldf_spec, N/2+1 float pairs, 8-byte aligned, even leading dimensions) -> mask rows
+ * (d_mask + s ld_mask + f ldf_mask, N/2+1 floats).  carry = 0: every stream starts at
+ * frame 0 with fresh state kept in registers; the object's state is neither read nor
+ * written, any n_streams.  carry = 1: n_streams must equal the channel count; the run
+ * continues from the object's state and frame counter and advances both.  One launch,
+ * CRLOT_K_DENOISE_GAINS: a lane per (stream, bin) column walks the frames in order (the
+ * recurrence is not linear, so a column is not chunked), adjacent lanes adjacent bins.
+ * n_streams or F of 0: CRLOT_OK, nothing written.  CRLOT_EINVAL: null buffers, a leading
+ * dimension too small or odd where pairs need it even, a mask that overlaps the spectra.
+ *
+ * crlot_denoise(dn, d_x, d_y, n_streams, T, ld_x, ld_y, stream) = crlot_stft -> the gains
+ * (carry = 0) -> crlot_istft_ola with the gains as the per-frame mask, spectra and gains
+ * in the stream's sliced workspace (slices under 256 MiB or one stream's worth); bit for
+ * bit the hand composition under either frame-pairing setting.  The mask is passed to the
+ * synthesis half as an argument, as crlot_hpss passes its masks: nothing is stored in the
+ * plan, and a plan that holds a stored mask of its own is CRLOT_EINVAL.  y gets F H
+ * samples per stream, F = crlot_frame_count(T).
+ *
+ * crlot_stream_denoise_hop(st, dn, d_hop_in, d_hop_out, emitted, stream): push_hop with
+ * frame k's gain row, computed from frame k's own spectrum, as the mask of the frame the
+ * hop completes.  A whole-mode call (it mixes with push_hop / push_hop_masked as far as
+ * the frame counters allow); a hop that completes no frame touches no state.  The frame
+ * index is the stream's.  CRLOT_EINVAL: a null argument, dn created on another plan,
+ * another channel count.  CRLOT_ERUNTIME: dn's frame counter differs from the frames the
+ * stream has completed (until both are reset), or the stream is in split mode.  Routes
+ * (crlot_denoiser_set_route: 0 the library's choice, 1 fused, 2 staged; CRLOT_EUNSUPPORTED
+ * for 1 at a shape without the fused kernel):
+ *   fused   one launch, CRLOT_K_DENOISE_HOP: the state planes of the lane's bins are read
+ *           where push_hop_masked reads its mask row, advanced between split and merge,
+ *           stored back; no spectrum in HBM.  Shapes: the register-resident hop's with
+ *           N <= 1024.  The library's choice there.
+ *   staged  three launches: the analysis half (CRLOT_K_STREAM_STFT) into the object's
+ *           spectrum rows, CRLOT_K_DENOISE_GAINS with F = 1 on the object's state, the
+ *           synthesis half (CRLOT_K_STREAM_ISTFT) with the gains as its mask row.  Every
+ *           other shape a stream accepts, N = 2048 and the mixed-radix ones included.
+ * Both routes give the same bits, equal to crlot_denoise's over the concatenated hops
+ * with frame pairing off in DROP mode.  crlot_denoiser_last_launch lists the last hop's
+ * (or the last crlot_denoise_gains call's) kernels and grids. */
+typedef struct crlot_denoiser crlot_denoiser;
+typedef struct crlot_denoise_desc {
+    double alpha_s;   /* smoothing of the power S along time */
+    double alpha_p;   /* smoothing of the speech-presence probability p */
+    double alpha_d;   /* floor of the noise estimate's smoothing factor */
+    double delta;     /* presence threshold on S / Smin */
+    double alpha_dd;  /* decision-directed weight of the a-priori SNR */
+    double g_min;     /* gain floor */
+    int32_t window;   /* minimum-tracking window L, frames */
+    int32_t reserved;
+} crlot_denoise_desc;
+typedef struct crlot_denoise_launch {
+    int32_t route;      /* 1 fused, 2 staged (hops); 0: the last call was crlot_denoise_gains, or none yet */
+    int32_t n_kernels;  /* 0: no launch yet; 1: gains, a fused hop, or a staged hop that completed no frame; 3: a staged hop */
+    int32_t kernel[3];  /* CRLOT_K_* in launch order */
+    int32_t reserved;
+    int64_t grid[3];    /* workgroups of each (0 for a mixed-radix hop half: its launcher sizes the workgroups) */
+} crlot_denoise_launch;
+int crlot_denoise_desc_default(crlot_denoise_desc* desc);
+int crlot_denoiser_create(crlot_plan* plan, const crlot_denoise_desc* desc, int32_t channels, crlot_denoiser** out);
+void crlot_denoiser_destroy(crlot_denoiser* dn);
+int crlot_denoiser_prepare(crlot_denoiser* dn);
+int crlot_denoiser_reset(crlot_denoiser* dn);
+int crlot_denoiser_info(const crlot_denoiser* dn, int32_t* channels, int32_t* bins, int64_t* frames,
+                        int32_t* route /* the setter's value */, int32_t* fused_ok);
+int crlot_denoiser_state(crlot_denoiser* dn, float** d_state /* [channels][6][N/2+1] */);
+int crlot_denoiser_set_route(crlot_denoiser* dn, int32_t route /* 0 auto, 1 fused, 2 staged */);
+int crlot_denoiser_last_launch(const crlot_denoiser* dn, crlot_denoise_launch* out);
+int crlot_denoise_gains(crlot_denoiser* dn, const float* d_spec, float* d_mask, int32_t n_streams, int64_t F,
+                        int64_t ld_spec, int64_t ldf_spec, int64_t ld_mask, int64_t ldf_mask, int32_t carry,
+                        void* stream);
+int crlot_denoise(crlot_denoiser* dn, const float* d_x, float* d_y, int32_t n_streams, int64_t T, int64_t ld_x,
+                  int64_t ld_y, void* stream);
+int crlot_stream_denoise_hop(crlot_stream* st, crlot_denoiser* dn, const float* d_hop_in, float* d_hop_out,
+                             int32_t* emitted, void* stream);
 
 /* host helpers (no device) */
 #define CRLOT_MEL_HTK 0

@@ -579,6 +579,79 @@ class Features {
     crlot_features* f_ = nullptr;
 };
 
+// The stationary-noise suppressor (crlot_denoiser_create; MCRA noise tracking and a
+// decision-directed Wiener gain): gains_device gives the mask rows of spectra,
+// denoise_device is stft -> gains -> masked istft_ola in one call, and
+// SpectralStream::denoise_hop runs it per hop on this object's state.  The plan (an
+// StftEngine's plan()) must outlive the object.
+class Denoiser {
+   public:
+    static crlot_denoise_desc defaults() {
+        crlot_denoise_desc d{};
+        check(crlot_denoise_desc_default(&d), "crlot_denoise_desc_default");
+        return d;
+    }
+    Denoiser(crlot_plan* plan, int channels, const crlot_denoise_desc& desc = defaults()) {
+        check(crlot_denoiser_create(plan, &desc, channels, &d_), "crlot_denoiser_create");
+    }
+    ~Denoiser() { crlot_denoiser_destroy(d_); }
+    Denoiser(const Denoiser&) = delete;
+    Denoiser& operator=(const Denoiser&) = delete;
+    Denoiser(Denoiser&& o) noexcept : d_(o.d_) { o.d_ = nullptr; }
+    Denoiser& operator=(Denoiser&& o) noexcept {
+        if (this != &o) {
+            crlot_denoiser_destroy(d_);
+            d_ = o.d_;
+            o.d_ = nullptr;
+        }
+        return *this;
+    }
+    void prepare() { check(crlot_denoiser_prepare(d_), "crlot_denoiser_prepare"); }
+    void reset() { check(crlot_denoiser_reset(d_), "crlot_denoiser_reset"); }
+    // 0: the library's choice, 1: fused (one launch), 2: staged (three)
+    void set_route(int route) { check(crlot_denoiser_set_route(d_, route), "crlot_denoiser_set_route"); }
+    int channels() const {
+        int32_t n = 0;
+        check(crlot_denoiser_info(d_, &n, nullptr, nullptr, nullptr, nullptr), "crlot_denoiser_info");
+        return n;
+    }
+    int bins() const {
+        int32_t n = 0;
+        check(crlot_denoiser_info(d_, nullptr, &n, nullptr, nullptr, nullptr), "crlot_denoiser_info");
+        return n;
+    }
+    int64_t frames() const {
+        int64_t n = 0;
+        check(crlot_denoiser_info(d_, nullptr, nullptr, &n, nullptr, nullptr), "crlot_denoiser_info");
+        return n;
+    }
+    // the carried state on the device: [channels][6][bins] floats (S, Smin, Stmp, p, lam, A2)
+    float* state() {
+        float* p = nullptr;
+        check(crlot_denoiser_state(d_, &p), "crlot_denoiser_state");
+        return p;
+    }
+    crlot_denoise_launch last_launch() const {
+        crlot_denoise_launch r{};
+        check(crlot_denoiser_last_launch(d_, &r), "crlot_denoiser_last_launch");
+        return r;
+    }
+    // spectra as crlot_stft lays them out -> mask rows of bins() floats; carry: continue from and advance the state
+    void gains_device(const float* d_spec, float* d_mask, int n_streams, int64_t F, int64_t ld_spec, int64_t ldf_spec,
+                      int64_t ld_mask, int64_t ldf_mask, bool carry = false, hipStream_t s = nullptr) {
+        check(crlot_denoise_gains(d_, d_spec, d_mask, n_streams, F, ld_spec, ldf_spec, ld_mask, ldf_mask, carry ? 1 : 0, s),
+              "crlot_denoise_gains");
+    }
+    void denoise_device(const float* d_x, float* d_y, int n_streams, int64_t T, int64_t ld_x, int64_t ld_y,
+                        hipStream_t s = nullptr) {
+        check(crlot_denoise(d_, d_x, d_y, n_streams, T, ld_x, ld_y, s), "crlot_denoise");
+    }
+    crlot_denoiser* get() const { return d_; }
+
+   private:
+    crlot_denoiser* d_ = nullptr;
+};
+
 // Real-time per-hop streaming with hops in host memory (BASELINE config 4):
 // the resident kernel behind crlot_stream_rt_*.  push_hop copies one hop of
 // channels x H samples in ([H][C] interleaved PCM or [C][H]), returns the H
@@ -651,6 +724,12 @@ class SpectralStream {
         int32_t em = 0;
         check(crlot_stream_features_hop(st_, f.get(), d_hop_in, d_feat, ld_feat, d_spec, ld_spec, &em, stream),
               "crlot_stream_features_hop");
+        return size_t(em);
+    }
+    // push_hop with the suppressor's gain row of the frame the hop completes; dn's state advances
+    size_t denoise_hop(Denoiser& dn, const float* d_hop_in, float* d_hop_out, void* stream = nullptr) {
+        int32_t em = 0;
+        check(crlot_stream_denoise_hop(st_, dn.get(), d_hop_in, d_hop_out, &em, stream), "crlot_stream_denoise_hop");
         return size_t(em);
     }
     void istft_hop(const float* d_spec, int64_t ld_spec, const float* d_mask, int64_t ld_mask, float* d_hop_out,
