@@ -151,6 +151,12 @@ class DenoiseLaunch(C.Structure):
                 ("grid", C.c_int64 * 3)]
 
 
+class XspecLaunch(C.Structure):
+    """crlot_xspec_launch (include/crlot_dsp.h): what a cross-spectrum object's last call launched."""
+    _fields_ = [("n_kernels", C.c_int32), ("kernel", C.c_int32 * 3), ("reserved", C.c_int32 * 2),
+                ("grid", C.c_int64 * 3)]
+
+
 class FftDesc(C.Structure):
     """crlot_fft_desc (include/crlot_dsp.h)."""
     _fields_ = [("domain", C.c_int32), ("nfft", C.c_int32), ("device", C.c_int32)]
@@ -270,6 +276,18 @@ def lib():
         "crlot_denoise_gains": ([vp, vp, vp, i32, i64, i64, i64, i64, i64, i32, vp], C.c_int),
         "crlot_denoise": ([vp, vp, vp, i32, i64, i64, i64, vp], C.c_int),
         "crlot_stream_denoise_hop": ([vp, vp, vp, vp, C.POINTER(i32), vp], C.c_int),
+        "crlot_xspec_create": ([vp, i32, C.c_double, C.POINTER(vp)], C.c_int),
+        "crlot_xspec_destroy": ([vp], None),
+        "crlot_xspec_prepare": ([vp], C.c_int),
+        "crlot_xspec_reset": ([vp], C.c_int),
+        "crlot_xspec_info": ([vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i64), fp, fp], C.c_int),
+        "crlot_xspec_state": ([vp, C.POINTER(vp)], C.c_int),
+        "crlot_xspec_last_launch": ([vp, C.POINTER(XspecLaunch)], C.c_int),
+        "crlot_xspec_accumulate": ([vp, vp, vp, i32, i64, i64, i64, i64, i64, i32, vp, vp], C.c_int),
+        "crlot_xspec_derive": ([vp, vp, i32, i32, vp, i64, vp, i64, vp, i64, vp], C.c_int),
+        "crlot_xspec_peak": ([vp, vp, i64, i32, i32, vp, i64, vp], C.c_int),
+        "crlot_xspec_estimate": ([vp, vp, vp, i32, i64, i64, i64, i32, vp, vp], C.c_int),
+        "crlot_xspec_delay": ([vp, vp, i32, i32, i32, vp, i64, vp], C.c_int),
         "crlot_resample_geometry": ([C.POINTER(ResamplerDesc), C.POINTER(ResamplerGeometry)], C.c_int),
         "crlot_resample_table_host": ([C.POINTER(ResamplerDesc), fp], C.c_int),
         "crlot_rational_approx": ([C.c_double, i32, C.POINTER(i32), C.POINTER(i32)], C.c_int),
@@ -2009,6 +2027,272 @@ class Denoiser:
         s = _stream_handle(x) if stream is None else stream
         _check(lib().crlot_denoise(self._h, x.data_ptr(), y.data_ptr(), S, T, _ld(x, 0, T), ld_y, s), "crlot_denoise")
         return y
+
+
+# ----------------------------------------------------------------- cross-spectral estimation
+XSPEC_PLANES = ("Saa", "Sbb", "Sr", "Si")
+XSPEC_NONE, XSPEC_PHAT = 0, 1
+
+
+def _xspec_rows_layout(shape, strides, dtype: str, device_index, plan_device: int, P: int, width: int, want: str,
+                       what: str):
+    """Validate one row per pair from its plain description (shape and strides in elements
+    as tuples, dtype name, device index or None for a host tensor): (P, width) of dtype
+    `want` on the plan's device, rows contiguous and at least `width` apart.  Returns the
+    row stride in elements."""
+    shape, strides = tuple(int(v) for v in shape), tuple(int(v) for v in strides)
+    if shape != (P, width) or len(strides) != 2:
+        raise ValueError(f"{what} must be ({P}, {width}), not {shape}")
+    if dtype != want:
+        raise ValueError(f"{what} must be {want}, not {dtype}")
+    if device_index is None or int(device_index) != int(plan_device):
+        raise ValueError(f"{what} must live on the plan's device {plan_device}, not "
+                         f"{'the host' if device_index is None else device_index}")
+    if width > 1 and strides[1] != 1:
+        raise ValueError(f"{what} must have contiguous rows")
+    ld = strides[0] if P > 1 else width  # (a size-1 dim's stride is meaningless)
+    if ld < width:
+        raise ValueError(f"{what} rows overlap: the row stride is below {width}")
+    return ld
+
+
+class CrossSpectrum:
+    """The cross-spectral estimator (crlot_xspec_create): averaged Saa, Sbb and Sab =
+    conj(A) B of `pairs` pairs of spectra along the frame axis (alpha 0: Welch sums, alpha
+    in (0, 1): exponential averaging), and what follows from them: coherence(), transfer()
+    (H1 = Sab / Saa), weighted() and delay() (GCC-PHAT: the lag of b against a, positive
+    when b is late).  accumulate takes spectra, estimate takes signals; carry=True
+    continues from and advances this object's state.  Creation checks alpha (ValueError)
+    and touches no device."""
+
+    def __init__(self, plan: "Plan", pairs: int, alpha: float = 0.0):
+        self._h = None
+        self.plan, self.pairs, self.alpha = plan, int(pairs), float(alpha)
+        self.bins = plan.frame_size // 2 + 1
+        h = C.c_void_p()
+        _check(lib().crlot_xspec_create(plan._h, int(pairs), float(alpha), C.byref(h)), "crlot_xspec_create")
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().crlot_xspec_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # interpreter shutdown
+            pass
+
+    def _info(self):
+        pairs, bins, frames = C.c_int32(), C.c_int32(), C.c_int64()
+        lam, om = C.c_float(), C.c_float()
+        _check(lib().crlot_xspec_info(self._h, C.byref(pairs), C.byref(bins), C.byref(frames), C.byref(lam),
+                                      C.byref(om)), "crlot_xspec_info")
+        return {"pairs": pairs.value, "bins": bins.value, "frames": frames.value, "lambda": lam.value,
+                "omega": om.value}
+
+    @property
+    def frames(self) -> int:
+        """Frames the carried state has seen since create / reset."""
+        return self._info()["frames"]
+
+    @property
+    def factors(self) -> tuple:
+        """(lambda, omega) as the kernels use them: (1, 1) for Welch sums."""
+        i = self._info()
+        return i["lambda"], i["omega"]
+
+    def prepare(self):
+        with _torch().cuda.device(self.plan._device_index()):
+            _check(lib().crlot_xspec_prepare(self._h), "crlot_xspec_prepare")
+
+    def reset(self):
+        """Zero the state and the frame counter."""
+        _check(lib().crlot_xspec_reset(self._h), "crlot_xspec_reset")
+
+    def state(self):
+        """The carried state on the device, a (pairs, 4, N/2+1) float32 torch view in
+        XSPEC_PLANES order (valid while this object lives, zeroed by reset)."""
+        torch = _torch()
+        ptr = C.c_void_p()
+        dev = self.plan._device_index()
+        with torch.cuda.device(dev):
+            _check(lib().crlot_xspec_state(self._h, C.byref(ptr)), "crlot_xspec_state")
+            return torch.as_tensor(_DeviceFloats(ptr.value, (self.pairs, 4, self.bins)), device=f"cuda:{dev}")
+
+    def last_launch(self) -> dict:
+        r = XspecLaunch()
+        _check(lib().crlot_xspec_last_launch(self._h, C.byref(r)), "crlot_xspec_last_launch")
+        kernels = [int(r.kernel[i]) for i in range(r.n_kernels)]
+        return {"kernels": kernels, "names": [kernel_name(k) for k in kernels],
+                "grids": [int(r.grid[i]) for i in range(r.n_kernels)]}
+
+    def _state_out(self, P: int, carry: bool, state_out, like, *inputs):
+        """The state output of accumulate / estimate: checked, or allocated when a fresh run needs one."""
+        torch = _torch()
+        if carry and P != self.pairs:
+            raise ValueError(f"carry needs {self.pairs} pairs, not {P}")
+        if state_out is None:
+            if carry:
+                return None
+            return torch.empty((P, 4, self.bins), dtype=torch.float32, device=like.device)
+        shape, strides, dtype, dev = _tensor_layout(state_out)
+        if shape != (P, 4, self.bins) or dtype != "float32" or not state_out.is_contiguous():
+            raise ValueError(f"state_out must be a contiguous ({P}, 4, {self.bins}) float32 tensor")
+        if dev is None or dev != self.plan._device_index():
+            raise ValueError("state_out must live on the plan's device")
+        if any(_tensors_overlap(state_out, t) for t in inputs):
+            raise ValueError("state_out overlaps an input")
+        return state_out
+
+    def accumulate(self, a, b, carry: bool = False, state_out=None, stream: int | None = None):
+        """a, b: (P, F, N/2+1) complex64 device tensors, Plan.stft's layout; a may be
+        (F, N/2+1): one reference shared by every pair.  carry=False: fresh state, any P, the
+        result in state_out (allocated when None), this object untouched.  carry=True: P must
+        be the pair count; the run continues from this object's state and advances it.
+        Returns the (P, 4, N/2+1) state the run ends with (the live view for carry=True
+        without a state_out)."""
+        if len(b.shape) == 2:
+            b = b[None]
+        dev = self.plan._device_index()
+        P, F = int(b.shape[0]), int(b.shape[1])
+        shared = len(a.shape) == 2
+        a3 = a[None] if shared else a
+        ld_b, ldf_b = _stretch_spec_layout(*_tensor_layout(b), dev, self.bins, "b")
+        ld_a, ldf_a = _stretch_spec_layout(*_tensor_layout(a3), dev, self.bins, "a",
+                                           expect=(1 if shared else P, F, self.bins))
+        out = self._state_out(P, carry, state_out, b, a, b)
+        s = _stream_handle(b) if stream is None else stream
+        _check(lib().crlot_xspec_accumulate(self._h, a.data_ptr(), b.data_ptr(), P, F, 0 if shared else ld_a, ldf_a, ld_b,
+                                            ldf_b, int(bool(carry)), None if out is None else out.data_ptr(), s),
+               "crlot_xspec_accumulate")
+        return self.state() if out is None else out
+
+    def estimate(self, xa, xb, carry: bool = False, state_out=None, stream: int | None = None):
+        """xa, xb: (P, T) float32 device tensors; xa may be (T,): one reference shared by every
+        pair.  accumulate(stft(xa), stft(xb)) bit for bit, with the spectra in the plan's
+        scratch.  Returns the state as accumulate does."""
+        if xb.dim() == 1:
+            xb = xb[None]
+        P, T = _spectrogram_x_layout(*_tensor_layout(xb))
+        shared = xa.dim() == 1
+        Pa, Ta = _spectrogram_x_layout(*_tensor_layout(xa[None] if shared else xa))
+        if Ta != T or (not shared and Pa != P):
+            raise ValueError("xa must be (T,) or match xb's (P, T)")
+        dev = self.plan._device_index()
+        for t, what in ((xa, "xa"), (xb, "xb")):
+            if (t.device.index if t.device.index is not None else 0) != dev:
+                raise ValueError(f"{what} must live on the plan's device {dev}")
+        ld_xb = _ld(xb, 0, T)
+        ld_xa = 0 if shared else _ld(xa, 0, T)
+        if ld_xb < T or (not shared and ld_xa < T):
+            raise ValueError("rows overlap: the stream stride is below T")
+        out = self._state_out(P, carry, state_out, xb, xa, xb)
+        s = _stream_handle(xb) if stream is None else stream
+        _check(lib().crlot_xspec_estimate(self._h, xa.data_ptr(), xb.data_ptr(), P, T, ld_xa, ld_xb, int(bool(carry)),
+                                          None if out is None else out.data_ptr(), s), "crlot_xspec_estimate")
+        return self.state() if out is None else out
+
+    def _state_in(self, state):
+        """(data pointer or None, P, a tensor on the device) of the state a derive / delay call reads."""
+        if state is None:
+            return None, self.pairs, self.state()
+        shape, strides, dtype, dev = _tensor_layout(state)
+        if len(shape) != 3 or shape[1:] != (4, self.bins) or dtype != "float32" or not state.is_contiguous():
+            raise ValueError(f"state must be a contiguous (P, 4, {self.bins}) float32 tensor")
+        if dev is None or dev != self.plan._device_index():
+            raise ValueError("state must live on the plan's device")
+        return state.data_ptr(), int(shape[0]), state
+
+    def derive(self, state=None, weighting: int = XSPEC_NONE, want=("coherence", "transfer", "weighted"),
+               coherence=None, transfer=None, weighted=None, stream: int | None = None) -> dict:
+        """The rows derived from a state block (None: this object's) in one pass: any of
+        "coherence" (P, N/2+1) float32, "transfer" (H1) and "weighted" (the cross-spectrum
+        under `weighting`: XSPEC_NONE or XSPEC_PHAT), both (P, N/2+1) complex64.  `want`
+        names the outputs; a tensor passed for one is written in place.  Returns a dict."""
+        torch = _torch()
+        names = ("coherence", "transfer", "weighted")
+        given = dict(zip(names, (coherence, transfer, weighted)))
+        want = set(want) | {k for k, v in given.items() if v is not None}
+        if not want or not want <= set(names):
+            raise ValueError(f"want must name at least one of {names}")
+        if int(weighting) not in (XSPEC_NONE, XSPEC_PHAT):
+            raise ValueError("weighting must be XSPEC_NONE or XSPEC_PHAT")
+        ptr, P, st = self._state_in(state)
+        dev = self.plan._device_index()
+        outs, args = {}, []
+        for k in names:
+            if k not in want:
+                args += [None, 0]
+                continue
+            cplx = k != "coherence"
+            t = given[k]
+            if t is None:
+                t = torch.empty((P, self.bins), dtype=torch.complex64 if cplx else torch.float32, device=st.device)
+            ld = _xspec_rows_layout(*_tensor_layout(t), dev, P, self.bins, "complex64" if cplx else "float32", k)
+            if _tensors_overlap(t, st) or any(_tensors_overlap(t, o) for o in outs.values()):
+                raise ValueError(f"{k} overlaps the state or another output")
+            outs[k] = t
+            args += [t.data_ptr(), 2 * ld if cplx else ld]
+        s = _stream_handle(st) if stream is None else stream
+        _check(lib().crlot_xspec_derive(self._h, ptr, P, int(weighting), *args, s), "crlot_xspec_derive")
+        return outs
+
+    def coherence(self, state=None, stream: int | None = None):
+        """The magnitude-squared coherence |Sab|^2 / (Saa Sbb), (P, N/2+1) float32, not clamped."""
+        return self.derive(state, want=("coherence",), stream=stream)["coherence"]
+
+    def transfer(self, state=None, stream: int | None = None):
+        """H1 = Sab / Saa, (P, N/2+1) complex64: Plan.irfft of it is the impulse response from a to b."""
+        return self.derive(state, want=("transfer",), stream=stream)["transfer"]
+
+    def weighted(self, state=None, weighting: int = XSPEC_PHAT, stream: int | None = None):
+        """The cross-spectrum under `weighting`, (P, N/2+1) complex64."""
+        return self.derive(state, weighting, want=("weighted",), stream=stream)["weighted"]
+
+    def _lag(self, max_lag) -> int:
+        n = self.plan.frame_size
+        m = n // 2 - 1 if max_lag is None else int(max_lag)
+        if not 1 <= m <= n // 2 - 1:
+            raise ValueError(f"max_lag must lie in [1, {n // 2 - 1}] (a longer search takes a longer frame)")
+        return m
+
+    def _peak_out(self, P: int, out, like):
+        if out is None:
+            return _torch().empty((P, 3), dtype=_torch().float32, device=like.device), 3
+        return out, _xspec_rows_layout(*_tensor_layout(out), self.plan._device_index(), P, 3, "float32", "out")
+
+    def peak(self, cc, max_lag=None, out=None, stream: int | None = None):
+        """cc: (P, N) float32 correlation rows -> (P, 3) float32 rows {lag, frac, value}: the
+        first maximum over the lags -max_lag .. max_lag (None: N/2 - 1) and its parabolic
+        refinement; lag + frac is the delay in samples."""
+        m = self._lag(max_lag)
+        if len(cc.shape) != 2:
+            raise ValueError("cc must be (P, N)")
+        P = int(cc.shape[0])
+        ld_cc = _xspec_rows_layout(*_tensor_layout(cc), self.plan._device_index(), P, self.plan.frame_size, "float32",
+                                   "cc")
+        out, ld_out = self._peak_out(P, out, cc)
+        if _tensors_overlap(out, cc):
+            raise ValueError("out overlaps cc")
+        s = _stream_handle(cc) if stream is None else stream
+        _check(lib().crlot_xspec_peak(self._h, cc.data_ptr(), ld_cc, P, m, out.data_ptr(), ld_out, s), "crlot_xspec_peak")
+        return out
+
+    def delay(self, state=None, weighting: int = XSPEC_PHAT, max_lag=None, out=None, stream: int | None = None):
+        """peak(Plan.irfft(weighted(state, weighting)), max_lag) bit for bit, the rows between
+        in the plan's scratch: (P, 3) float32 rows {lag, frac, value} of b against a."""
+        m = self._lag(max_lag)
+        if int(weighting) not in (XSPEC_NONE, XSPEC_PHAT):
+            raise ValueError("weighting must be XSPEC_NONE or XSPEC_PHAT")
+        ptr, P, st = self._state_in(state)
+        out, ld_out = self._peak_out(P, out, st)
+        if _tensors_overlap(out, st):
+            raise ValueError("out overlaps the state")
+        s = _stream_handle(st) if stream is None else stream
+        _check(lib().crlot_xspec_delay(self._h, ptr, P, int(weighting), m, out.data_ptr(), ld_out, s), "crlot_xspec_delay")
+        return out
 
 
 class FftPlan:

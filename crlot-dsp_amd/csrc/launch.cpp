@@ -193,6 +193,9 @@ extern "C" const char* crlot_kernel_name(int32_t id) {
         case CRLOT_K_DENOISE_HOP: return "k_stream_denoise";
         case CRLOT_K_STREAM_STFT: return "k_stream_stft";
         case CRLOT_K_STREAM_ISTFT: return "k_stream_istft";
+        case CRLOT_K_XSPEC_ACC: return "k_xspec_acc";
+        case CRLOT_K_XSPEC_DERIVE: return "k_xspec_derive";
+        case CRLOT_K_XSPEC_PEAK: return "k_xspec_peak";
         case CRLOT_K_EXPERIMENT: return "k_experiment";
         default: return "unknown";
     }

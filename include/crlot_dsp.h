@@ -276,6 +276,9 @@ int crlot_test_inject(int32_t what, int32_t count);
 #define CRLOT_K_DENOISE_HOP 54  /* crlot_stream_denoise_hop, fused: the hop with the gain computed in the mask row's place */
 #define CRLOT_K_STREAM_STFT 55  /* ... staged: the hop's analysis half (crlot_stream_stft_hop's kernel) */
 #define CRLOT_K_STREAM_ISTFT 56 /* ... staged: the synthesis half with the gains as its mask row */
+#define CRLOT_K_XSPEC_ACC 57    /* crlot_xspec_accumulate: the four averaged planes over two spectra, a lane per column */
+#define CRLOT_K_XSPEC_DERIVE 58 /* crlot_xspec_derive: coherence, H1 and the weighted cross-spectrum from a state block */
+#define CRLOT_K_XSPEC_PEAK 59   /* crlot_xspec_peak: the arg-max over the lags of a correlation row, a wave per pair */
 #define CRLOT_K_EXPERIMENT 99   /* experiment builds only */
 typedef struct crlot_launch_info {
     int32_t n_kernels;
@@ -1249,6 +1252,117 @@ int crlot_denoise(crlot_denoiser* dn, const float* d_x, float* d_y, int32_t n_st
                   int64_t ld_y, void* stream);
 int crlot_stream_denoise_hop(crlot_stream* st, crlot_denoiser* dn, const float* d_hop_in, float* d_hop_out,
                              int32_t* emitted, void* stream);
+
+/* ---------------------------------------------------------------- cross-spectral estimation
+ * Averaged auto- and cross-spectra of two signals along the frame axis of crlot_stft's
+ * spectra, and what a voice chain derives from them: the magnitude-squared coherence (the
+ * double-talk / "is this reference useful" statistic), the H1 transfer-function estimate
+ * Sab / Saa (what crlot_fdaf converges to: a warm start for crlot_fdaf_set_taps), and the
+ * GCC-PHAT estimate of the bulk delay of b against a.  Per (pair, bin b <= N/2) four
+ * float32 values -- Saa, Sbb, Sr, Si -- are carried from frame to frame.
+ *
+ * Values.  float32, every product, sum, difference and quotient rounded on its own (no
+ * FMA), division and sqrtf correctly rounded; max(a, b) is a > b ? a : b.  A (reference)
+ * and B (desired) are rows crlot_stft / crlot_stream_stft_hop store: before the plan gain.
+ * State: a block [pair][4][N/2+1] in the order Saa, Sbb, Sr, Si, all 0 after create / reset.
+ *   1  terms of frame k:  Taa = (ar ar) + (ai ai);  Tbb = (br br) + (bi bi);
+ *      Tr = (ar br) + (ai bi);  Ti = (ar bi) - (ai br)          -- conj(A) B, as scipy's
+ *      csd(x, y): H1 is the transfer function from a to b, and b delayed against a gives
+ *      a positive lag;
+ *   2  each plane S = (lambda S) + (omega T).  alpha = 0 (Welch): lambda = omega = 1, both
+ *      products exact, the planes are plain sums in frame order (the mean is the caller's
+ *      division by the frame count; nothing below needs it).  alpha in (0, 1): lambda =
+ *      float32(alpha), omega = float32(1 - alpha) formed in double.  No first-frame case:
+ *      from zero state (lambda 0) + (omega T) is omega T;
+ *   3  rows derived from a state block, tiny = 1e-30f, m2 = (Sr Sr) + (Si Si):
+ *      coherence C = m2 / max(Saa Sbb, tiny), not clamped to 1;
+ *      transfer  d = max(Saa, tiny), H1 = (Sr / d, Si / d), a spectrum row of N/2+1 float
+ *        pairs (what crlot_irfft_batched takes);
+ *      weighted cross-spectrum W, a spectrum row: weighting 0: (Sr, Si); weighting 1 (PHAT):
+ *        m = sqrtf(m2), e = max(m, tiny), W = (Sr / e, Si / e);
+ *   4  peak of a row cc[n], n < N, over max_lag in [1, N/2 - 1]: position j = 0 .. 2 max_lag
+ *      is lag l = j - max_lag with value v_j = cc[l mod N].  The winner starts as j = 0; a
+ *      later j replaces it only if v_j > the best value so far: the smallest j among equal
+ *      maxima wins and a NaN at j > 0 never wins (a NaN at j = 0 is never replaced: nothing
+ *      compares greater).  With y0, y1, y2 = cc at l - 1, l, l + 1 (mod N): den = (y0 -
+ *      (2 y1)) + y2, frac = den == 0 ? 0 : (0.5 (y0 - y2)) / den.  Output row per pair:
+ *      three floats {float(l), frac, y1}; the delay in samples is the sum of the first two.
+ * Output bits do not depend on the grid, the pair count, the leading dimensions, a pair's
+ * position, a shared or a repeated reference, or where a run is cut: F frames equal F1
+ * frames followed by F - F1 with the state carried.
+ *
+ * crlot_xspec_create(plan, n_pairs, alpha, out) touches no device.  alpha is checked first:
+ * NaN, Inf, < 0 or >= 1 is CRLOT_EINVAL with no plan needed; then a null argument, n_pairs
+ * < 1, a state size or grid that does not fit.  prepare, or the first call that needs it,
+ * makes one allocation: the state block, zeroed.  crlot_xspec_state returns its device
+ * pointer; crlot_xspec_reset synchronises the device, zeroes the block and the frame
+ * counter.  A single-owner object like crlot_stream; graph capture is not supported (the
+ * frame counter is by value).
+ *
+ * crlot_xspec_accumulate(xs, d_a, d_b, n_pairs, F, ld_a, ldf_a, ld_b, ldf_b, carry,
+ * d_state_out, stream): spectra in crlot_stft's layout (frame f of pair p at d + p ld +
+ * f ldf, N/2+1 float pairs, 8-byte aligned, even leading dimensions); ld_a = 0: one
+ * reference stream shared by every pair, as a mask's ld_stream = 0.  carry = 0: every pair
+ * starts from zero state kept in registers, any n_pairs, the result goes to d_state_out
+ * (required, [n_pairs][4][N/2+1]), the object is untouched.  carry = 1: n_pairs must equal
+ * the object's; the run continues from the object's state and counter and advances both;
+ * d_state_out may be NULL (else it receives a copy of the new state).  One launch,
+ * CRLOT_K_XSPEC_ACC: a lane per (pair, bin) column walks the frames in order.  F = 1 with
+ * carry = 1 on the rows of two crlot_stream_stft_hop streams is the per-hop tracker.
+ * n_pairs or F of 0: CRLOT_OK, nothing written.  CRLOT_EINVAL: null buffers, a leading
+ * dimension too small or odd, a state output that overlaps an input.
+ *
+ * crlot_xspec_derive(xs, d_state, n_pairs, weighting, d_coh, ld_coh, d_h1, ld_h1, d_w, ld_w,
+ * stream): d_state NULL: the object's state (n_pairs must equal the object's).  Any
+ * non-empty subset of the three outputs in one pass (CRLOT_K_XSPEC_DERIVE); row p at d +
+ * p ld: coherence N/2+1 floats, H1 and W N/2+1 float pairs (8-byte aligned, even ld).
+ * CRLOT_EINVAL: no output, weighting outside 0 / 1, a leading dimension too small or odd,
+ * outputs that overlap each other or the state.
+ *
+ * crlot_xspec_peak(xs, d_cc, ld_cc, n_pairs, max_lag, d_out, ld_out, stream): step 4 on
+ * caller rows of N floats (CRLOT_K_XSPEC_PEAK, a wave per pair); ld_out >= 3.  Lags are
+ * limited to +-(N/2 - 1) of the plan's frame: a longer search takes a plan with a longer
+ * frame.
+ *
+ * crlot_xspec_estimate(xs, d_xa, d_xb, n_pairs, T, ld_xa, ld_xb, carry, d_state_out,
+ * stream) = crlot_stft(a) -> crlot_stft(b) -> accumulate over F = crlot_frame_count(T)
+ * frames; ld_xa = 0: a shared reference (one transform of it).  The spectra stay in the
+ * stream's sliced workspace (slices of pairs under 256 MiB or one pair's worth); bit for
+ * bit the hand composition under either frame-pairing setting.
+ *
+ * crlot_xspec_delay(xs, d_state, n_pairs, weighting, max_lag, d_out, ld_out, stream) =
+ * derive(W) -> crlot_irfft_batched on the object's plan -> peak, W and cc in the stream's
+ * scratch; every N crlot_irfft_batched accepts on that plan; bit for bit the hand
+ * composition.  crlot_xspec_last_launch lists the last call's kernels of this subsystem
+ * and their grids (the transforms of estimate and delay are in crlot_plan_last_launch). */
+typedef struct crlot_xspec crlot_xspec;
+typedef struct crlot_xspec_launch {
+    int32_t n_kernels;    /* 0: no launch yet */
+    int32_t kernel[3];    /* CRLOT_K_* in launch order */
+    int32_t reserved[2];
+    int64_t grid[3];      /* workgroups of each */
+} crlot_xspec_launch;
+int crlot_xspec_create(crlot_plan* plan, int32_t n_pairs, double alpha, crlot_xspec** out);
+void crlot_xspec_destroy(crlot_xspec* xs);
+int crlot_xspec_prepare(crlot_xspec* xs);
+int crlot_xspec_reset(crlot_xspec* xs);
+int crlot_xspec_info(const crlot_xspec* xs, int32_t* pairs, int32_t* bins, int64_t* frames, float* lambda,
+                     float* omega);
+int crlot_xspec_state(crlot_xspec* xs, float** d_state /* [pairs][4][N/2+1] */);
+int crlot_xspec_last_launch(const crlot_xspec* xs, crlot_xspec_launch* out);
+int crlot_xspec_accumulate(crlot_xspec* xs, const float* d_a, const float* d_b, int32_t n_pairs, int64_t F,
+                           int64_t ld_a /* 0: shared */, int64_t ldf_a, int64_t ld_b, int64_t ldf_b, int32_t carry,
+                           float* d_state_out /* carry = 1: may be NULL */, void* stream);
+int crlot_xspec_derive(crlot_xspec* xs, const float* d_state /* NULL: the object's */, int32_t n_pairs,
+                       int32_t weighting /* 0 none, 1 PHAT */, float* d_coh, int64_t ld_coh, float* d_h1,
+                       int64_t ld_h1, float* d_w, int64_t ld_w, void* stream);
+int crlot_xspec_peak(crlot_xspec* xs, const float* d_cc, int64_t ld_cc, int32_t n_pairs, int32_t max_lag,
+                     float* d_out /* [n_pairs][ld_out >= 3] */, int64_t ld_out, void* stream);
+int crlot_xspec_estimate(crlot_xspec* xs, const float* d_xa, const float* d_xb, int32_t n_pairs, int64_t T,
+                         int64_t ld_xa /* 0: shared */, int64_t ld_xb, int32_t carry, float* d_state_out,
+                         void* stream);
+int crlot_xspec_delay(crlot_xspec* xs, const float* d_state /* NULL: the object's */, int32_t n_pairs,
+                      int32_t weighting, int32_t max_lag, float* d_out, int64_t ld_out, void* stream);
 
 /* host helpers (no device) */
 #define CRLOT_MEL_HTK 0

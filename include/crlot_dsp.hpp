@@ -652,6 +652,90 @@ class Denoiser {
     crlot_denoiser* d_ = nullptr;
 };
 
+// The cross-spectral estimator (crlot_xspec_create): averaged Saa, Sbb and Sab of pairs
+// of spectra along the frame axis, and the coherence, the H1 transfer function and the
+// GCC-PHAT delay derived from them.  alpha 0: Welch sums; alpha in (0, 1): exponential
+// averaging.  The plan (an StftEngine's plan()) must outlive the object.
+class CrossSpectrum {
+   public:
+    CrossSpectrum(crlot_plan* plan, int pairs, double alpha = 0.0) {
+        check(crlot_xspec_create(plan, pairs, alpha, &x_), "crlot_xspec_create");
+    }
+    ~CrossSpectrum() { crlot_xspec_destroy(x_); }
+    CrossSpectrum(const CrossSpectrum&) = delete;
+    CrossSpectrum& operator=(const CrossSpectrum&) = delete;
+    CrossSpectrum(CrossSpectrum&& o) noexcept : x_(o.x_) { o.x_ = nullptr; }
+    CrossSpectrum& operator=(CrossSpectrum&& o) noexcept {
+        if (this != &o) {
+            crlot_xspec_destroy(x_);
+            x_ = o.x_;
+            o.x_ = nullptr;
+        }
+        return *this;
+    }
+    void prepare() { check(crlot_xspec_prepare(x_), "crlot_xspec_prepare"); }
+    void reset() { check(crlot_xspec_reset(x_), "crlot_xspec_reset"); }
+    int pairs() const {
+        int32_t n = 0;
+        check(crlot_xspec_info(x_, &n, nullptr, nullptr, nullptr, nullptr), "crlot_xspec_info");
+        return n;
+    }
+    int bins() const {
+        int32_t n = 0;
+        check(crlot_xspec_info(x_, nullptr, &n, nullptr, nullptr, nullptr), "crlot_xspec_info");
+        return n;
+    }
+    int64_t frames() const {
+        int64_t n = 0;
+        check(crlot_xspec_info(x_, nullptr, nullptr, &n, nullptr, nullptr), "crlot_xspec_info");
+        return n;
+    }
+    // the carried state on the device: [pairs][4][bins] floats (Saa, Sbb, Sr, Si)
+    float* state() {
+        float* p = nullptr;
+        check(crlot_xspec_state(x_, &p), "crlot_xspec_state");
+        return p;
+    }
+    crlot_xspec_launch last_launch() const {
+        crlot_xspec_launch r{};
+        check(crlot_xspec_last_launch(x_, &r), "crlot_xspec_last_launch");
+        return r;
+    }
+    // spectra as crlot_stft lays them out (ld_a 0: one shared reference); carry: continue
+    // from and advance the state (d_state_out may be null), else fresh into d_state_out
+    void accumulate_device(const float* d_a, const float* d_b, int n_pairs, int64_t F, int64_t ld_a, int64_t ldf_a,
+                           int64_t ld_b, int64_t ldf_b, bool carry, float* d_state_out, hipStream_t s = nullptr) {
+        check(crlot_xspec_accumulate(x_, d_a, d_b, n_pairs, F, ld_a, ldf_a, ld_b, ldf_b, carry ? 1 : 0, d_state_out, s),
+              "crlot_xspec_accumulate");
+    }
+    // stft(a) -> stft(b) -> accumulate, the spectra in the plan's scratch (ld_xa 0: a shared reference)
+    void estimate_device(const float* d_xa, const float* d_xb, int n_pairs, int64_t T, int64_t ld_xa, int64_t ld_xb,
+                         bool carry, float* d_state_out, hipStream_t s = nullptr) {
+        check(crlot_xspec_estimate(x_, d_xa, d_xb, n_pairs, T, ld_xa, ld_xb, carry ? 1 : 0, d_state_out, s),
+              "crlot_xspec_estimate");
+    }
+    // d_state null: the object's; any of the three outputs may be null (not all)
+    void derive_device(const float* d_state, int n_pairs, int weighting, float* d_coh, int64_t ld_coh, float* d_h1,
+                       int64_t ld_h1, float* d_w, int64_t ld_w, hipStream_t s = nullptr) {
+        check(crlot_xspec_derive(x_, d_state, n_pairs, weighting, d_coh, ld_coh, d_h1, ld_h1, d_w, ld_w, s),
+              "crlot_xspec_derive");
+    }
+    // rows of N floats -> {lag, frac, value} per pair, lags within +-max_lag <= N/2 - 1
+    void peak_device(const float* d_cc, int64_t ld_cc, int n_pairs, int max_lag, float* d_out, int64_t ld_out,
+                     hipStream_t s = nullptr) {
+        check(crlot_xspec_peak(x_, d_cc, ld_cc, n_pairs, max_lag, d_out, ld_out, s), "crlot_xspec_peak");
+    }
+    // derive(W) -> inverse transform -> peak
+    void delay_device(const float* d_state, int n_pairs, int weighting, int max_lag, float* d_out, int64_t ld_out,
+                      hipStream_t s = nullptr) {
+        check(crlot_xspec_delay(x_, d_state, n_pairs, weighting, max_lag, d_out, ld_out, s), "crlot_xspec_delay");
+    }
+    crlot_xspec* get() const { return x_; }
+
+   private:
+    crlot_xspec* x_ = nullptr;
+};
+
 // Real-time per-hop streaming with hops in host memory (BASELINE config 4):
 // the resident kernel behind crlot_stream_rt_*.  push_hop copies one hop of
 // channels x H samples in ([H][C] interleaved PCM or [C][H]), returns the H
