@@ -157,6 +157,18 @@ class XspecLaunch(C.Structure):
                 ("grid", C.c_int64 * 3)]
 
 
+class BeamformDesc(C.Structure):
+    """crlot_beamform_desc (include/crlot_dsp.h)."""
+    _fields_ = [("mics", C.c_int32), ("ref", C.c_int32), ("mode", C.c_int32), ("update_every", C.c_int32),
+                ("alpha", C.c_double), ("loading", C.c_double)]
+
+
+class BeamformLaunch(C.Structure):
+    """crlot_beamform_launch (include/crlot_dsp.h): what a beamformer's last call launched."""
+    _fields_ = [("n_kernels", C.c_int32), ("kernel", C.c_int32 * 3), ("reserved", C.c_int32 * 2),
+                ("grid", C.c_int64 * 3)]
+
+
 class FftDesc(C.Structure):
     """crlot_fft_desc (include/crlot_dsp.h)."""
     _fields_ = [("domain", C.c_int32), ("nfft", C.c_int32), ("device", C.c_int32)]
@@ -288,6 +300,22 @@ def lib():
         "crlot_xspec_peak": ([vp, vp, i64, i32, i32, vp, i64, vp], C.c_int),
         "crlot_xspec_estimate": ([vp, vp, vp, i32, i64, i64, i64, i32, vp, vp], C.c_int),
         "crlot_xspec_delay": ([vp, vp, i32, i32, i32, vp, i64, vp], C.c_int),
+        "crlot_beamform_desc_default": ([C.POINTER(BeamformDesc)], C.c_int),
+        "crlot_beamformer_create": ([vp, C.POINTER(BeamformDesc), i32, C.POINTER(vp)], C.c_int),
+        "crlot_beamformer_destroy": ([vp], None),
+        "crlot_beamformer_prepare": ([vp], C.c_int),
+        "crlot_beamformer_reset": ([vp], C.c_int),
+        "crlot_beamformer_info": ([vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i64), fp, fp, fp],
+                                  C.c_int),
+        "crlot_beamformer_state": ([vp, C.POINTER(vp)], C.c_int),
+        "crlot_beamformer_weights": ([vp, C.POINTER(vp)], C.c_int),
+        "crlot_beamformer_steering": ([vp, C.POINTER(vp)], C.c_int),
+        "crlot_beamformer_last_launch": ([vp, C.POINTER(BeamformLaunch)], C.c_int),
+        "crlot_beamform_accumulate": ([vp, vp, i64, i64, vp, i64, i64, i32, i64, i32, i32, vp, vp], C.c_int),
+        "crlot_beamform_solve": ([vp, vp, vp, i32, vp, vp], C.c_int),
+        "crlot_beamform_apply": ([vp, vp, i64, i64, vp, i32, i64, vp, i64, i64, vp], C.c_int),
+        "crlot_beamform": ([vp, vp, i64, vp, i64, i64, vp, i64, i32, i64, vp], C.c_int),
+        "crlot_stream_beamform_hop": ([vp, vp, vp, vp, vp, i64, vp, C.POINTER(i32), vp], C.c_int),
         "crlot_resample_geometry": ([C.POINTER(ResamplerDesc), C.POINTER(ResamplerGeometry)], C.c_int),
         "crlot_resample_table_host": ([C.POINTER(ResamplerDesc), fp], C.c_int),
         "crlot_rational_approx": ([C.c_double, i32, C.POINTER(i32), C.POINTER(i32)], C.c_int),
@@ -2293,6 +2321,358 @@ class CrossSpectrum:
         s = _stream_handle(st) if stream is None else stream
         _check(lib().crlot_xspec_delay(self._h, ptr, P, int(weighting), m, out.data_ptr(), ld_out, s), "crlot_xspec_delay")
         return out
+
+
+# ----------------------------------------------------------------- beamformer
+BF_SOUDEN, BF_STEERED = 0, 1
+BF_TARGET_BOTH, BF_TARGET_SPEECH, BF_TARGET_NOISE = 0, 1, 2
+_BF_MODES = {"souden": BF_SOUDEN, "steered": BF_STEERED, BF_SOUDEN: BF_SOUDEN, BF_STEERED: BF_STEERED}
+
+
+def steering_from_delays(delays, nfft: int):
+    """The steering vectors exp(-2 pi i b tau / N) of microphones delayed by tau samples
+    against the reference microphone (what CrossSpectrum.delay returns against it: lag +
+    frac): delays (..., M) -> (..., M, N/2+1) complex64, computed in float64 and rounded
+    once.  A host helper: no device, and no bit parity with anything else is claimed."""
+    if int(nfft) < 2 or int(nfft) % 2:
+        raise ValueError("nfft must be even and at least 2")
+    tau = np.asarray(delays, np.float64)[..., None]
+    if not np.all(np.isfinite(tau)):
+        raise ValueError("delays must be finite")
+    b = np.arange(int(nfft) // 2 + 1, dtype=np.float64)
+    return np.exp(-2j * np.pi * b * tau / int(nfft)).astype(np.complex64)
+
+
+def _bf_spec_layout(shape, strides, dtype: str, device_index, plan_device: int, M: int, bins: int, what: str = "spec"):
+    """Validate the beamformer's spectra from their plain description (shape and strides in
+    complex elements as tuples, dtype name, device index or None for a host tensor): (G, M,
+    F, bins) complex64 on the plan's device, rows contiguous and at least `bins` apart,
+    microphones not overlapping and the groups M microphone strides apart (stream g M + m).
+    Returns (G, F, ld_spec, ldf_spec) in floats."""
+    shape, strides = tuple(int(v) for v in shape), tuple(int(v) for v in strides)
+    if len(shape) != 4 or len(strides) != 4 or shape[1] != M or shape[3] != bins or min(shape) < 1:
+        raise ValueError(f"{what} must be (G, {M}, F, {bins}) or ({M}, F, {bins}) complex64")
+    if dtype != "complex64":
+        raise ValueError(f"{what} must be complex64, not {dtype}")
+    if device_index is None or int(device_index) != int(plan_device):
+        raise ValueError(f"{what} must live on the plan's device {plan_device}, not "
+                         f"{'the host' if device_index is None else device_index}")
+    if strides[3] != 1:
+        raise ValueError(f"{what} must have contiguous rows")
+    G, F = shape[0], shape[2]
+    ldf = strides[2] if F > 1 else bins
+    ld = strides[1]
+    if ldf < bins or ld < (F - 1) * ldf + bins:
+        raise ValueError(f"{what} rows overlap")
+    if G > 1 and strides[0] != M * ld:
+        raise ValueError(f"{what}: the groups must be {M} microphone strides apart (stream g M + m)")
+    return G, F, 2 * ld, 2 * ldf
+
+
+def _bf_mask_layout(shape, strides, dtype: str, device_index, plan_device: int, G: int, F: int, bins: int):
+    """The same for a mask: (G, F, bins) float32, or (F, bins): one set of rows for every
+    group.  Returns (ld_mask, ldf_mask), ld_mask 0 for a shared mask."""
+    shape, strides = tuple(int(v) for v in shape), tuple(int(v) for v in strides)
+    if shape not in ((G, F, bins), (F, bins)) or len(strides) != len(shape):
+        raise ValueError(f"mask must be ({G}, {F}, {bins}) or ({F}, {bins}), not {shape}")
+    if dtype != "float32":
+        raise ValueError(f"mask must be float32, not {dtype}")
+    if device_index is None or int(device_index) != int(plan_device):
+        raise ValueError(f"mask must live on the plan's device {plan_device}, not "
+                         f"{'the host' if device_index is None else device_index}")
+    if strides[-1] != 1:
+        raise ValueError("mask must have contiguous rows")
+    ldf = strides[-2] if F > 1 else bins
+    if ldf < bins:
+        raise ValueError("mask rows overlap")
+    if len(shape) == 2:
+        return 0, ldf
+    ld = strides[0] if G > 1 else F * ldf
+    if G > 1 and ld == 0:
+        return 0, ldf  # (an expanded mask: one set of rows)
+    if ld < (F - 1) * ldf + bins:
+        raise ValueError("mask rows overlap")
+    return (ld if G > 1 else 0), ldf
+
+
+class Beamformer:
+    """The mask-driven MVDR beamformer (crlot_beamformer_create): `groups` independent
+    arrays of `mics` microphones (2..8), one output per group.  accumulate averages the
+    target and noise spatial covariance matrices per bin from spectra (Plan.stft's layout,
+    (G, M, F, N/2+1)) under a mask ((G, F, N/2+1) or shared (F, N/2+1)), solve turns a state
+    into weights (mode "souden": mask-based, against microphone `ref`; "steered": the
+    classical MVDR towards steering()), apply forms y = w^H x per frame, beamform runs
+    stft -> accumulate -> solve -> apply -> istft_ola on signals, hop is the per-hop chain.
+    Creation checks the descriptor (ValueError) and touches no device."""
+
+    def __init__(self, plan: "Plan", mics: int, groups: int = 1, ref: int = 0, mode="souden", alpha: float = 0.0,
+                 loading: float = 1e-3, update_every: int = 1):
+        self._h = None
+        if isinstance(mode, str):
+            mode = mode.lower()
+        if mode not in _BF_MODES:
+            raise ValueError('mode must be "souden" or "steered"')
+        self.plan, self.mics, self.groups, self.ref = plan, int(mics), int(groups), int(ref)
+        self.mode, self.alpha, self.loading, self.update_every = _BF_MODES[mode], float(alpha), float(loading), int(update_every)
+        self.bins = plan.frame_size // 2 + 1
+        d = BeamformDesc(self.mics, self.ref, self.mode, self.update_every, self.alpha, self.loading)
+        h = C.c_void_p()
+        _check(lib().crlot_beamformer_create(plan._h, C.byref(d), self.groups, C.byref(h)), "crlot_beamformer_create")
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().crlot_beamformer_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # interpreter shutdown
+            pass
+
+    def _info(self):
+        g, m, b, fr = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
+        lam, om, ld = C.c_float(), C.c_float(), C.c_float()
+        _check(lib().crlot_beamformer_info(self._h, C.byref(g), C.byref(m), C.byref(b), C.byref(fr), C.byref(lam),
+                                           C.byref(om), C.byref(ld)), "crlot_beamformer_info")
+        return {"groups": g.value, "mics": m.value, "bins": b.value, "frames": fr.value, "lambda": lam.value,
+                "omega": om.value, "loading": ld.value}
+
+    @property
+    def frames(self) -> int:
+        """Frames the carried state has seen since create / reset."""
+        return self._info()["frames"]
+
+    @property
+    def factors(self) -> tuple:
+        """(lambda, omega, loading) as the kernels use them."""
+        i = self._info()
+        return i["lambda"], i["omega"], i["loading"]
+
+    def prepare(self):
+        with _torch().cuda.device(self.plan._device_index()):
+            _check(lib().crlot_beamformer_prepare(self._h), "crlot_beamformer_prepare")
+
+    def reset(self):
+        """Zero the state and the frame counter, restore the pass-through weights (the steering block stays)."""
+        _check(lib().crlot_beamformer_reset(self._h), "crlot_beamformer_reset")
+
+    def _view(self, fn, name, shape, cplx):
+        torch = _torch()
+        ptr = C.c_void_p()
+        dev = self.plan._device_index()
+        with torch.cuda.device(dev):
+            _check(fn(self._h, C.byref(ptr)), name)
+            t = torch.as_tensor(_DeviceFloats(ptr.value, shape + ((2,) if cplx else ())), device=f"cuda:{dev}")
+        return torch.view_as_complex(t) if cplx else t
+
+    def state(self):
+        """The carried state on the device, a (groups, 2, M M, N/2+1) float32 torch view: the
+        target matrix then the noise matrix, each the M diagonals, then Re, Im of every i < j."""
+        return self._view(lib().crlot_beamformer_state, "crlot_beamformer_state",
+                          (self.groups, 2, self.mics * self.mics, self.bins), False)
+
+    def weights(self):
+        """The object's weights, a (groups, M, N/2+1) complex64 torch view."""
+        return self._view(lib().crlot_beamformer_weights, "crlot_beamformer_weights", (self.groups, self.mics, self.bins),
+                          True)
+
+    def steering(self):
+        """The object's steering vectors (STEERED mode), a (groups, M, N/2+1) complex64 torch view."""
+        return self._view(lib().crlot_beamformer_steering, "crlot_beamformer_steering",
+                          (self.groups, self.mics, self.bins), True)
+
+    def _set(self, view, value, what):
+        torch = _torch()
+        v = torch.as_tensor(np.ascontiguousarray(value, np.complex64)) if not torch.is_tensor(value) else value
+        if v.dtype != torch.complex64:
+            raise ValueError(f"{what} must be complex64")
+        if tuple(v.shape) == (self.mics, self.bins):
+            v = v[None].expand(self.groups, -1, -1)
+        if tuple(v.shape) != (self.groups, self.mics, self.bins):
+            raise ValueError(f"{what} must be ({self.groups}, {self.mics}, {self.bins}) or ({self.mics}, {self.bins})")
+        view.copy_(v.to(view.device))
+
+    def set_weights(self, w):
+        """Replace the object's weights: (groups, M, N/2+1) or (M, N/2+1) complex64, host or device."""
+        self._set(self.weights(), w, "weights")
+
+    def set_steering(self, d):
+        """Replace the object's steering vectors (see steering_from_delays)."""
+        self._set(self.steering(), d, "steering")
+
+    def last_launch(self) -> dict:
+        r = BeamformLaunch()
+        _check(lib().crlot_beamformer_last_launch(self._h, C.byref(r)), "crlot_beamformer_last_launch")
+        kernels = [int(r.kernel[i]) for i in range(r.n_kernels)]
+        return {"kernels": kernels, "names": [kernel_name(k) for k in kernels],
+                "grids": [int(r.grid[i]) for i in range(r.n_kernels)]}
+
+    def _spec(self, spec, what="spec"):
+        if len(spec.shape) == 3:
+            spec = spec[None]
+        G, F, ld, ldf = _bf_spec_layout(*_tensor_layout(spec), self.plan._device_index(), self.mics, self.bins, what)
+        return spec, G, F, ld, ldf
+
+    def _block(self, t, G, cplx, what):
+        """A caller's state / weights / steering block: (data pointer, tensor), checked."""
+        shape = (G, self.mics, self.bins) if cplx else (G, 2, self.mics * self.mics, self.bins)
+        want = "complex64" if cplx else "float32"
+        tshape, _, dtype, dev = _tensor_layout(t)
+        if tshape != shape or dtype != want or not t.is_contiguous():
+            raise ValueError(f"{what} must be a contiguous {shape} {want} tensor")
+        if dev is None or dev != self.plan._device_index():
+            raise ValueError(f"{what} must live on the plan's device")
+        return t.data_ptr()
+
+    def accumulate(self, spec, mask=None, target: int = BF_TARGET_BOTH, carry: bool = False, state_out=None,
+                   stream: int | None = None):
+        """spec: (G, M, F, N/2+1) or (M, F, N/2+1) complex64 device tensor, Plan.stft's rows of
+        stream g M + m.  mask: (G, F, N/2+1) float32, or (F, N/2+1) shared by every group;
+        None (targets 1, 2): 1.  target BF_TARGET_BOTH: the target matrix with weight mask
+        and the noise matrix with 1 - mask; BF_TARGET_SPEECH / BF_TARGET_NOISE: that matrix
+        alone with weight mask.  carry=False: fresh state, any G, the result in state_out
+        (allocated zeroed when None), this object untouched.  carry=True: G must be the group
+        count; the run continues from this object's state and advances it.  Returns the
+        (G, 2, M M, N/2+1) state the run ends with (the live view for carry=True without a
+        state_out)."""
+        torch = _torch()
+        spec, G, F, ld, ldf = self._spec(spec)
+        if int(target) not in (0, 1, 2):
+            raise ValueError("target must be BF_TARGET_BOTH, BF_TARGET_SPEECH or BF_TARGET_NOISE")
+        if int(target) == 0 and mask is None:
+            raise ValueError("target BF_TARGET_BOTH needs a mask")
+        if carry and G != self.groups:
+            raise ValueError(f"carry needs {self.groups} groups, not {G}")
+        mp, ldm, ldfm = None, 0, 0
+        if mask is not None:
+            ldm, ldfm = _bf_mask_layout(*_tensor_layout(mask), self.plan._device_index(), G, F, self.bins)
+            mp = mask.data_ptr()
+        out = state_out
+        if out is None and not carry:
+            out = torch.zeros((G, 2, self.mics * self.mics, self.bins), dtype=torch.float32, device=spec.device)
+        op = None
+        if out is not None:
+            op = self._block(out, G, False, "state_out")
+            if _tensors_overlap(out, spec) or (mask is not None and _tensors_overlap(out, mask)):
+                raise ValueError("state_out overlaps an input")
+        s = _stream_handle(spec) if stream is None else stream
+        _check(lib().crlot_beamform_accumulate(self._h, spec.data_ptr(), ld, ldf, mp, ldm, ldfm, G, F, int(target),
+                                               int(bool(carry)), op, s), "crlot_beamform_accumulate")
+        return self.state() if out is None else out
+
+    def solve(self, state=None, steering=None, weights=None, stream: int | None = None):
+        """The weights of a state block (None: this object's) in this object's mode; steering
+        (STEERED mode; None: this object's) and weights (None: this object's, which is
+        returned) are (G, M, N/2+1) complex64 device tensors."""
+        G = self.groups if state is None else int(state.shape[0])
+        sp = None if state is None else self._block(state, G, False, "state")
+        dp = None if steering is None else self._block(steering, G, True, "steering")
+        wp = None if weights is None else self._block(weights, G, True, "weights")
+        if weights is not None and any(t is not None and _tensors_overlap(weights, t) for t in (state, steering)):
+            raise ValueError("weights overlap the state or the steering block")
+        if G != self.groups and (state is None or weights is None or (steering is None and self.mode == BF_STEERED)):
+            raise ValueError(f"this object's blocks need {self.groups} groups, not {G}")
+        like = next((t for t in (state, weights, steering) if t is not None), None)
+        s = stream if stream is not None else (_stream_handle(like) if like is not None else _stream_handle(self.state()))
+        with _torch().cuda.device(self.plan._device_index()):
+            _check(lib().crlot_beamform_solve(self._h, sp, dp, G, wp, s), "crlot_beamform_solve")
+        return self.weights() if weights is None else weights
+
+    def apply(self, spec, weights=None, out=None, stream: int | None = None):
+        """spec as accumulate's -> (G, F, N/2+1) complex64: sum over m of conj(w_m) x_m per frame
+        and bin, with `weights` ((G, M, N/2+1) complex64; None: this object's)."""
+        torch = _torch()
+        squeeze = len(spec.shape) == 3
+        spec, G, F, ld, ldf = self._spec(spec)
+        wp = None if weights is None else self._block(weights, G, True, "weights")
+        if weights is None and G != self.groups:
+            raise ValueError(f"this object's weights need {self.groups} groups, not {G}")
+        if out is None:
+            out = torch.empty((G, F, self.bins), dtype=torch.complex64, device=spec.device)
+        o3 = out[None] if len(out.shape) == 2 else out
+        ld_o, ldf_o = _stretch_spec_layout(*_tensor_layout(o3), self.plan._device_index(), self.bins, "out",
+                                           expect=(G, F, self.bins))
+        if _tensors_overlap(o3, spec) or (weights is not None and _tensors_overlap(o3, weights)):
+            raise ValueError("out overlaps an input")
+        s = _stream_handle(spec) if stream is None else stream
+        _check(lib().crlot_beamform_apply(self._h, spec.data_ptr(), ld, ldf, wp, G, F, o3.data_ptr(), ld_o, ldf_o, s),
+               "crlot_beamform_apply")
+        return o3[0] if squeeze and len(out.shape) == 3 else out
+
+    def beamform(self, x, mask=None, y=None, stream: int | None = None):
+        """x: (G, M, T) or (M, T) float32 device tensor -> y: (G, F H): istft_ola of apply(stft(x))
+        under solve(accumulate(stft(x), mask)), bit for bit, everything between in the plan's
+        scratch; this object's state and weights are untouched.  mask as accumulate's; None
+        is allowed in STEERED mode only (the noise matrix from every frame with weight 1: the
+        minimum-power form).  The plan must have no stored spectral mask."""
+        torch = _torch()
+        squeeze = x.dim() == 2
+        if squeeze:
+            x = x[None]
+        shape, strides, dtype, dev = _tensor_layout(x)
+        if len(shape) != 3 or shape[1] != self.mics or dtype != "float32" or dev is None:
+            raise ValueError(f"x must be a (G, {self.mics}, T) or ({self.mics}, T) float32 device tensor")
+        if dev != self.plan._device_index():
+            raise ValueError(f"x must live on the plan's device {self.plan._device_index()}")
+        G, T = int(shape[0]), int(shape[2])
+        if T > 1 and strides[2] != 1:
+            raise ValueError("x must have contiguous rows")
+        ld_x = int(strides[1])
+        if ld_x < T or (G > 1 and int(strides[0]) != self.mics * ld_x):
+            raise ValueError(f"x: rows overlap, or the groups are not {self.mics} microphone strides apart")
+        if getattr(self.plan, "_mask", None) is not None:
+            raise ValueError("beamform: the plan has a stored spectral mask; clear it first")
+        if mask is None and self.mode != BF_STEERED:
+            raise ValueError("SOUDEN mode needs a mask")
+        if self.mode == BF_STEERED and G != self.groups:
+            raise ValueError(f"STEERED mode reads this object's steering block: {self.groups} groups, not {G}")
+        F = self.plan.frame_count(T)
+        L = F * self.plan.hop_size
+        mp, ldm, ldfm = None, 0, 0
+        if mask is not None:
+            ldm, ldfm = _bf_mask_layout(*_tensor_layout(mask), dev, G, F, self.bins)
+            mp = mask.data_ptr()
+        if y is None:
+            y = torch.empty((G, L), dtype=x.dtype, device=x.device)
+        y2 = y[None] if y.dim() == 1 else y
+        ld_y = _gl_y_layout(*_tensor_layout(y2), dev, G, L)
+        if _tensors_overlap(y2, x) or (mask is not None and _tensors_overlap(y2, mask)):
+            raise ValueError("y overlaps an input")
+        s = _stream_handle(x) if stream is None else stream
+        _check(lib().crlot_beamform(self._h, x.data_ptr(), ld_x, mp, ldm, ldfm, y2.data_ptr(), ld_y, G, T, s),
+               "crlot_beamform")
+        return y2[0] if squeeze and y.dim() == 2 else y
+
+    def hop(self, st_in: "Stream", st_out: "Stream", hop, mask, out=None, stream: int | None = None) -> tuple:
+        """One hop of the per-hop chain (crlot_stream_beamform_hop): st_in a Stream of groups x
+        mics channels (its analysis half), st_out one of groups channels (its synthesis
+        half), both on this object's plan; hop as st_in.stft_hop's; mask the frame's row(s),
+        (groups, N/2+1) or shared (N/2+1,) float32.  The state advances by one frame, the
+        weights are solved again every update_every frames.  Returns (out, emitted): out as
+        st_out's hops, written when emitted is H."""
+        torch = _torch()
+        if not isinstance(st_in, Stream) or not isinstance(st_out, Stream):
+            raise ValueError("st_in and st_out must be Stream objects")
+        if st_in.plan is not self.plan or st_out.plan is not self.plan:
+            raise ValueError("the streams must be on the beamformer's plan")
+        if st_in.channels != self.groups * self.mics or st_out.channels != self.groups:
+            raise ValueError(f"st_in needs {self.groups * self.mics} channels and st_out {self.groups}")
+        hop = st_in._hop_arg(hop)
+        if mask is None:
+            raise ValueError("hop needs a mask row")
+        mp, ldm = st_out._mask_arg(mask, hop)
+        H = self.plan.hop_size
+        if out is None:
+            out = torch.empty((H, self.groups) if st_out.interleaved else (self.groups, H), dtype=torch.float32,
+                              device=hop.device)
+        st_out._hop_arg(out, "out")
+        em = C.c_int32()
+        s = _stream_handle(hop) if stream is None else stream
+        _check(lib().crlot_stream_beamform_hop(st_in._h, st_out._h, self._h, hop.data_ptr(), mp, ldm, out.data_ptr(),
+                                               C.byref(em), s), "crlot_stream_beamform_hop")
+        return out, em.value
 
 
 class FftPlan:

@@ -196,6 +196,10 @@ extern "C" const char* crlot_kernel_name(int32_t id) {
         case CRLOT_K_XSPEC_ACC: return "k_xspec_acc";
         case CRLOT_K_XSPEC_DERIVE: return "k_xspec_derive";
         case CRLOT_K_XSPEC_PEAK: return "k_xspec_peak";
+        case CRLOT_K_BF_ACC: return "k_bf_acc";
+        case CRLOT_K_BF_SOLVE: return "k_bf_solve";
+        case CRLOT_K_BF_APPLY: return "k_bf_apply";
+        case CRLOT_K_BF_HOP: return "k_bf_hop";
         case CRLOT_K_EXPERIMENT: return "k_experiment";
         default: return "unknown";
     }

@@ -7,6 +7,7 @@
 #include <chrono>
 #include <cstring>
 
+#include "beamform_launch.h"
 #include "plan_internal.h"
 
 using namespace crlot;
@@ -324,6 +325,65 @@ int crlot_stream_denoise_hop(crlot_stream* st, crlot_denoiser* dn, const float* 
     if (k >= 0) dn->frames += 1;
     if (emitted) *emitted = k >= 0 ? int32_t(H) : 0;
     st->q += 1;
+    return CRLOT_OK;
+}
+
+// One hop of the beamforming chain (the contract is in include/crlot_dsp.h,
+// "beamformer"): the analysis half of st_in into the beamformer's spectrum rows, K_bf_hop
+// on its state and weights, the synthesis half of st_out from its output rows.
+int crlot_stream_beamform_hop(crlot_stream* st_in, crlot_stream* st_out, crlot_beamformer* bf, const float* d_in,
+                              const float* d_mask, int64_t ld_mask, float* d_out, int32_t* emitted, void* stream) {
+    if (emitted) *emitted = 0;
+    if (!st_in || !st_out) return fail(CRLOT_EINVAL, "null stream");
+    if (!bf) return fail(CRLOT_EINVAL, "null beamformer");
+    if (!d_in || !d_out || !d_mask) return fail(CRLOT_EINVAL, "null buffer");
+    if (st_in == st_out) return fail(CRLOT_EINVAL, "the two halves need a stream object each");
+    crlot::BfHopView v{};
+    if (int rc = crlot::beamformer_hop_view(bf, &v)) return rc;
+    crlot_plan* p = st_in->plan;
+    if (v.plan != p || st_out->plan != p) return fail(CRLOT_EINVAL, "the beamformer and the streams must share one plan");
+    if (st_in->channels != int64_t(v.groups) * v.mics)
+        return fail(CRLOT_EINVAL, "the input stream must have groups x mics channels");
+    if (st_out->channels != v.groups) return fail(CRLOT_EINVAL, "the output stream must have one channel per group");
+    if (int rc = check_mask_row(st_in, d_mask, ld_mask)) return rc;
+    if (ld_mask < 0) return fail(CRLOT_EINVAL, "ld_mask must be 0 (one shared row) or at least N/2 + 1 floats");
+    if (v.groups == 1) ld_mask = 0;  // (one group: not read)
+    const int64_t H = p->geo.h, done = drop_frames_after(st_in->q, p->geo.n, H);
+    if (v.frames != done || st_out->kf != done || (st_in->mode == 2 && st_in->kf != 0) ||
+        (st_out->mode == 2 && st_out->q != 0))
+        return fail(CRLOT_ERUNTIME, "the beamformer's and the streams' frame counters differ; reset all three");
+    if (int rc = stream_enter(st_in, 2)) return rc;
+    if (int rc = stream_enter(st_out, 2)) return rc;
+    DeviceGuard g(p->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int64_t row = int64_t(p->geo.n) + 2;
+    const int64_t k = stream_frame_of_hop(st_in, st_in->q);
+    crlot_beamform_launch rec{};
+    const auto hop_grid = [](const crlot_stream* st) { return st->any ? int64_t(0) : (int64_t(st->channels) + 3) / 4; };
+    {
+        const int64_t C = st_in->channels;
+        const int64_t ld = st_in->interleaved ? 1 : H, inc = st_in->interleaved ? C : 1;
+        hipError_t e = crlot::launch_stream_stft_hop(p->geo, tables(p), p->d_twany, st_in->any, d_in, ld, inc, v.d_spec,
+                                                     row, st_in->d_hist, st_in->channels, st_in->q, k, s);
+        if (e != hipSuccess) return hip_fail(e, "stream kernel launch");
+        rec.n_kernels = 1;
+        rec.kernel[0] = CRLOT_K_STREAM_STFT;
+        rec.grid[0] = hop_grid(st_in);
+    }
+    st_in->q += 1;
+    if (k >= 0) {
+        if (int rc = crlot::beamformer_hop_run(bf, d_mask, ld_mask, &rec, s)) return rc;
+        const int64_t C = st_out->channels;
+        const int64_t ld = st_out->interleaved ? 1 : H, inc = st_out->interleaved ? C : 1;
+        hipError_t e = crlot::launch_stream_istft_hop(p->geo, tables(p), p->d_twany, st_out->any, v.d_out, row, nullptr,
+                                                      0, d_out, ld, inc, st_out->d_acc, st_out->channels, st_out->kf, s);
+        if (e != hipSuccess) return hip_fail(e, "stream kernel launch");
+        st_out->kf += 1;
+        rec.kernel[rec.n_kernels] = CRLOT_K_STREAM_ISTFT;
+        rec.grid[rec.n_kernels++] = hop_grid(st_out);
+        if (emitted) *emitted = int32_t(H);
+    }
+    crlot::beamformer_set_last(bf, rec);
     return CRLOT_OK;
 }
 

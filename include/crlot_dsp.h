@@ -279,6 +279,10 @@ int crlot_test_inject(int32_t what, int32_t count);
 #define CRLOT_K_XSPEC_ACC 57    /* crlot_xspec_accumulate: the four averaged planes over two spectra, a lane per column */
 #define CRLOT_K_XSPEC_DERIVE 58 /* crlot_xspec_derive: coherence, H1 and the weighted cross-spectrum from a state block */
 #define CRLOT_K_XSPEC_PEAK 59   /* crlot_xspec_peak: the arg-max over the lags of a correlation row, a wave per pair */
+#define CRLOT_K_BF_ACC 60       /* crlot_beamform_accumulate: the two spatial covariance matrices per bin, a lane per matrix column */
+#define CRLOT_K_BF_SOLVE 61     /* crlot_beamform_solve: loading, Cholesky and the MVDR weights of a bin in registers */
+#define CRLOT_K_BF_APPLY 62     /* crlot_beamform_apply: y = w^H x per frame, the weights of a bin in registers */
+#define CRLOT_K_BF_HOP 63       /* crlot_stream_beamform_hop: one frame's update, the solve when due and the apply */
 #define CRLOT_K_EXPERIMENT 99   /* experiment builds only */
 typedef struct crlot_launch_info {
     int32_t n_kernels;
@@ -1363,6 +1367,161 @@ int crlot_xspec_estimate(crlot_xspec* xs, const float* d_xa, const float* d_xb, 
                          void* stream);
 int crlot_xspec_delay(crlot_xspec* xs, const float* d_state /* NULL: the object's */, int32_t n_pairs,
                       int32_t weighting, int32_t max_lag, float* d_out, int64_t ld_out, void* stream);
+
+/* ---------------------------------------------------------------- beamformer
+ * A mask-driven frequency-domain MVDR beamformer: G independent groups (arrays) of M
+ * microphones, 2 <= M <= 8, combined into one output stream per group.  The inputs are what
+ * the library already makes -- spectra in crlot_stft's layout, mask rows such as
+ * crlot_denoise_gains', inter-microphone delays from crlot_xspec_delay (as a steering
+ * vector) -- and the output is a spectrum row for crlot_istft_ola / crlot_stream_istft_hop.
+ * The reference project has no beamformer: nothing in this section restates it, and no
+ * entry below cites it.
+ *
+ * Terms.  Stream g M + m is microphone m of group g: frame f of stream s at d_spec + s
+ * ld_spec + f ldf_spec, N/2+1 float pairs, as crlot_stft / crlot_stream_stft_hop store them
+ * (before the plan gain).  ref is the reference microphone, 0 <= ref < M.
+ *
+ * Values.  float32, every product, sum, difference and quotient rounded on its own (no
+ * FMA), division and sqrtf correctly rounded; max(a, b) is a > b ? a : b; tiny = 1e-30f.
+ * Complex products, each product rounded before the sum or difference:
+ *   a conj(b) = ((a.re b.re) + (a.im b.im), (a.im b.re) - (a.re b.im))
+ *   conj(a) b = ((a.re b.re) + (a.im b.im), (a.re b.im) - (a.im b.re))
+ *   a b       = ((a.re b.re) - (a.im b.im), (a.re b.im) + (a.im b.re))
+ * and a complex value is subtracted, added or divided by a real per component.
+ * State: per (group, bin b <= N/2) two Hermitian matrices, Phi_s (target) then Phi_n
+ * (noise), each M M float planes: the M real diagonals Phi_00 .. Phi_{M-1,M-1}, then for
+ * every i < j in lexicographic order Re Phi_ij, Im Phi_ij.  The block is
+ * [group][2][M M][N/2+1], all 0 after create / reset.
+ *   1  terms of frame k, Phi_ij averaging x_i conj(x_j): diagonal T = (re re) + (im im);
+ *      i < j: T = x_i conj(x_j) as above;
+ *   2  update.  mu is the mask value of (group, frame, bin), 1 without a mask; nu = 1 - mu.
+ *      target 0: Phi_s with weight mu and Phi_n with weight nu (a mask is required);
+ *      target 1: Phi_s alone, weight mu;  target 2: Phi_n alone, weight mu (calibration on a
+ *      noise-only stretch).  Each plane S = (lambda S) + (omega (wgt T)); lambda and omega
+ *      from alpha as crlot_xspec forms them (alpha = 0: 1 and 1, Welch sums; alpha in (0, 1):
+ *      float32(alpha), float32(1 - alpha) formed in double).  No first-frame case;
+ *   3  solve per (group, bin).  tr = Phi_n00, then + Phi_n11 ... in index order; ld =
+ *      max(loading_f32 (tr / float(M)), tiny); A_ii = Phi_nii + ld, A_ij = Phi_nij.
+ *      Cholesky A = L L^H, j ascending: s = A_jj, then for k < j ascending s = s -
+ *      ((L_jk.re L_jk.re) + (L_jk.im L_jk.im)); d_j = sqrtf(max(s, tiny)); for i > j:
+ *      c = A_ij = conj(A_ji), then for k < j ascending c = c - L_ik conj(L_jk); L_ij = c / d_j.
+ *      Forward L z = r: i ascending, t = r_i, for k < i ascending t = t - L_ik z_k, z_i =
+ *      t / d_i.  Back L^H y = z: i descending, t = z_i, for k > i ascending t = t -
+ *      conj(L_ki) y_k, y_i = t / d_i.
+ *      mode 0 (SOUDEN; Souden, Benesty, Affes 2010): solve for every column c of Phi_s (read
+ *      from the Hermitian storage, the lower part the conjugate, the diagonal's imaginary
+ *      part 0); trace = Re y(0)_0, then + Re y(c)_c in c order; den = max(trace, tiny); w =
+ *      y(ref) / den.
+ *      mode 1 (STEERED, the classical MVDR): r = d, the steering vector of the bin
+ *      ([group][M][N/2+1] float pairs); q = (d_0.re y_0.re) + (d_0.im y_0.im), then + the
+ *      same of m = 1 .. in m order; den = max(q, tiny); w = y / den.  Only Phi_n is read.
+ *      Weights are a block [group][M][N/2+1] float pairs; after create / reset (1, 0) at
+ *      ref and 0 elsewhere, which passes the reference microphone through;
+ *   4  apply.  Y = sum over m ascending of conj(w_m) x_m, accumulated per component from
+ *      (0, 0), stored as N/2+1 float pairs.  The imaginary parts of DC and Nyquist are
+ *      stored as computed; crlot_istft_ola and crlot_stream_istft_hop ignore them.
+ * Output bits do not depend on the grid, the group count, a group's position, the leading
+ * dimensions, a shared or a repeated mask, where a run is cut (F frames equal F1 frames
+ * followed by F - F1 with the state carried), or how the matrix entries are spread over
+ * lanes.
+ *
+ * crlot_beamformer_create(plan, desc, groups, out) touches no device.  The descriptor is
+ * checked first, with no plan needed: mics outside 2..8, ref outside 0..mics-1, mode
+ * outside 0 / 1, update_every < 1, alpha NaN / Inf / < 0 / >= 1, loading NaN / Inf / < 0 are
+ * CRLOT_EINVAL; then a null argument, groups < 1, a size or grid that does not fit.
+ * prepare, or the first call that needs it, makes one allocation: the state, the weights
+ * (set to pass ref through), the steering block (zero) and the rows of the per-hop entry.
+ * _state, _weights and _steering return device pointers the caller may read and write
+ * (crlot_beamformer_steering is how a STEERED object gets its vectors); _reset synchronises
+ * the device, zeroes the state, restores the pass-through weights and zeroes the frame
+ * counter (the steering block is kept).  A single-owner object like crlot_stream; graph
+ * capture is not supported (the frame counter is by value).
+ *
+ * crlot_beamform_accumulate(bf, d_spec, ld_spec, ldf_spec, d_mask, ld_mask, ldf_mask,
+ * n_groups, F, target, carry, d_state_out, stream): steps 1 and 2 over F frames of n_groups
+ * M streams (CRLOT_K_BF_ACC).  The mask value of group g, frame f, bin b is d_mask[g ld_mask
+ * + f ldf_mask + b]; ld_mask = 0: one set of rows shared by every group; d_mask NULL: 1
+ * (targets 1 and 2).  carry = 0: every group starts from zero state kept in registers, any
+ * n_groups, the result goes to d_state_out (required), the object is untouched; a matrix
+ * the target does not update is not written.  carry = 1: n_groups must equal the
+ * object's; the run continues from the object's state and counter and advances both;
+ * d_state_out may be NULL (else it receives a copy of the new state).  n_groups or F of 0:
+ * CRLOT_OK, nothing written.  CRLOT_EINVAL: null buffers, a leading dimension too small or
+ * (spectra) odd, target outside 0..2 or 0 without a mask, a state output that overlaps an
+ * input or the object's state.
+ *
+ * crlot_beamform_solve(bf, d_state, d_steer, n_groups, d_w, stream): step 3 in the
+ * object's mode (CRLOT_K_BF_SOLVE); NULL for a block means the object's (then n_groups must
+ * equal the object's).  crlot_beamform_apply(bf, d_spec, ld_spec, ldf_spec, d_w, n_groups,
+ * F, d_out, ld_out, ldf_out, stream): step 4 (CRLOT_K_BF_APPLY), frame f of group g at d_out
+ * + g ld_out + f ldf_out.  CRLOT_EINVAL: outputs that overlap an input, the state or the
+ * weights.
+ *
+ * crlot_beamform(bf, d_x, ld_x, d_mask, ld_mask, ldf_mask, d_y, ld_y, n_groups, T, stream) =
+ * crlot_stft of the n_groups M signals (stream s at d_x + s ld_x) -> accumulate (carry = 0,
+ * target 0) -> solve -> apply -> crlot_istft_ola of the n_groups outputs (group g at d_y +
+ * g ld_y, F H samples).  In STEERED mode d_mask may be NULL: Phi_n is then accumulated from
+ * every frame with weight 1 (target 2), the "minimum power" MPDR form, which cancels the
+ * target too wherever the steering vector is off.  Everything between stays in the
+ * stream's sliced workspace, sliced by group (slices under 256 MiB or one group's worth);
+ * bit for bit the hand composition under either frame-pairing setting.  The object's
+ * state, weights and counter are untouched (its steering block is read).  A plan that
+ * holds a stored spectral mask is CRLOT_EINVAL, as for crlot_denoise.
+ *
+ * crlot_stream_beamform_hop(st_in, st_out, bf, d_hop_in, d_mask, ld_mask, d_hop_out,
+ * emitted, stream): one hop of the per-hop chain.  st_in has groups M channels and uses
+ * only its analysis half, st_out has groups channels and only its synthesis half; both in
+ * split mode on bf's plan.  A hop = crlot_stream_stft_hop into the object's rows ->
+ * CRLOT_K_BF_HOP -> crlot_stream_istft_hop: three launches, bit for bit stft_hop ->
+ * accumulate(F = 1, carry = 1, target 0) -> solve when due -> apply(F = 1) -> istft_hop.
+ * d_mask is the frame's mask row per group (ld_mask 0: shared), required.  The solve runs
+ * when (frames so far + 1) mod update_every == 0, after the update and before the apply.
+ * A hop that completes no frame runs only the analysis half, leaves d_hop_out untouched
+ * and sets *emitted = 0 (else the hop size).  CRLOT_EINVAL: channel counts or plans that do
+ * not match; CRLOT_ERUNTIME: frame counters that differ (reset all three), a stream in
+ * whole-hop mode.  crlot_beamformer_last_launch lists the last call's kernels and grids. */
+#define CRLOT_BF_SOUDEN 0
+#define CRLOT_BF_STEERED 1
+typedef struct crlot_beamform_desc {
+    int32_t mics;          /* M, 2..8 */
+    int32_t ref;           /* the reference microphone */
+    int32_t mode;          /* CRLOT_BF_SOUDEN, CRLOT_BF_STEERED */
+    int32_t update_every;  /* >= 1: hops between the per-hop entry's solves */
+    double alpha;          /* [0, 1): 0 Welch sums, else exponential averaging */
+    double loading;        /* >= 0, finite: diagonal loading relative to trace / M (default 1e-3) */
+} crlot_beamform_desc;
+typedef struct crlot_beamformer crlot_beamformer;
+typedef struct crlot_beamform_launch {
+    int32_t n_kernels;    /* 0: no launch yet */
+    int32_t kernel[3];    /* CRLOT_K_* in launch order */
+    int32_t reserved[2];
+    int64_t grid[3];      /* workgroups of each */
+} crlot_beamform_launch;
+int crlot_beamform_desc_default(crlot_beamform_desc* d);
+int crlot_beamformer_create(crlot_plan* plan, const crlot_beamform_desc* desc, int32_t groups, crlot_beamformer** out);
+void crlot_beamformer_destroy(crlot_beamformer* bf);
+int crlot_beamformer_prepare(crlot_beamformer* bf);
+int crlot_beamformer_reset(crlot_beamformer* bf);
+int crlot_beamformer_info(const crlot_beamformer* bf, int32_t* groups, int32_t* mics, int32_t* bins, int64_t* frames,
+                          float* lambda, float* omega, float* loading);
+int crlot_beamformer_state(crlot_beamformer* bf, float** d_state /* [groups][2][M M][N/2+1] */);
+int crlot_beamformer_weights(crlot_beamformer* bf, float** d_w /* [groups][M][N/2+1] float pairs */);
+int crlot_beamformer_steering(crlot_beamformer* bf, float** d_steer /* [groups][M][N/2+1] float pairs */);
+int crlot_beamformer_last_launch(const crlot_beamformer* bf, crlot_beamform_launch* out);
+int crlot_beamform_accumulate(crlot_beamformer* bf, const float* d_spec, int64_t ld_spec, int64_t ldf_spec,
+                              const float* d_mask, int64_t ld_mask /* 0: shared */, int64_t ldf_mask, int32_t n_groups,
+                              int64_t F, int32_t target, int32_t carry, float* d_state_out /* carry = 1: may be NULL */,
+                              void* stream);
+int crlot_beamform_solve(crlot_beamformer* bf, const float* d_state /* NULL: the object's */,
+                         const float* d_steer /* NULL: the object's */, int32_t n_groups,
+                         float* d_w /* NULL: the object's */, void* stream);
+int crlot_beamform_apply(crlot_beamformer* bf, const float* d_spec, int64_t ld_spec, int64_t ldf_spec,
+                         const float* d_w /* NULL: the object's */, int32_t n_groups, int64_t F, float* d_out,
+                         int64_t ld_out, int64_t ldf_out, void* stream);
+int crlot_beamform(crlot_beamformer* bf, const float* d_x, int64_t ld_x, const float* d_mask, int64_t ld_mask,
+                   int64_t ldf_mask, float* d_y, int64_t ld_y, int32_t n_groups, int64_t T, void* stream);
+int crlot_stream_beamform_hop(crlot_stream* st_in, crlot_stream* st_out, crlot_beamformer* bf, const float* d_hop_in,
+                              const float* d_mask, int64_t ld_mask, float* d_hop_out, int32_t* emitted, void* stream);
 
 /* host helpers (no device) */
 #define CRLOT_MEL_HTK 0

@@ -736,6 +736,117 @@ class CrossSpectrum {
     crlot_xspec* x_ = nullptr;
 };
 
+// The mask-driven MVDR beamformer (crlot_beamformer_create): groups of 2..8 microphones,
+// one output per group; the spatial covariance matrices per bin, the weights solved from
+// them (mask-based against a reference microphone, or steered) and y = w^H x per frame.
+// The plan (an StftEngine's plan()) must outlive the object.
+class Beamformer {
+   public:
+    Beamformer(crlot_plan* plan, int mics, int groups = 1, int ref = 0, int mode = CRLOT_BF_SOUDEN, double alpha = 0.0,
+               double loading = 1e-3, int update_every = 1) {
+        crlot_beamform_desc d{};
+        check(crlot_beamform_desc_default(&d), "crlot_beamform_desc_default");
+        d.mics = mics, d.ref = ref, d.mode = mode, d.update_every = update_every;
+        d.alpha = alpha, d.loading = loading;
+        check(crlot_beamformer_create(plan, &d, groups, &b_), "crlot_beamformer_create");
+    }
+    Beamformer(crlot_plan* plan, const crlot_beamform_desc& d, int groups) {
+        check(crlot_beamformer_create(plan, &d, groups, &b_), "crlot_beamformer_create");
+    }
+    ~Beamformer() { crlot_beamformer_destroy(b_); }
+    Beamformer(const Beamformer&) = delete;
+    Beamformer& operator=(const Beamformer&) = delete;
+    Beamformer(Beamformer&& o) noexcept : b_(o.b_) { o.b_ = nullptr; }
+    Beamformer& operator=(Beamformer&& o) noexcept {
+        if (this != &o) {
+            crlot_beamformer_destroy(b_);
+            b_ = o.b_;
+            o.b_ = nullptr;
+        }
+        return *this;
+    }
+    void prepare() { check(crlot_beamformer_prepare(b_), "crlot_beamformer_prepare"); }
+    void reset() { check(crlot_beamformer_reset(b_), "crlot_beamformer_reset"); }
+    int groups() const {
+        int32_t n = 0;
+        check(crlot_beamformer_info(b_, &n, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr), "crlot_beamformer_info");
+        return n;
+    }
+    int mics() const {
+        int32_t n = 0;
+        check(crlot_beamformer_info(b_, nullptr, &n, nullptr, nullptr, nullptr, nullptr, nullptr), "crlot_beamformer_info");
+        return n;
+    }
+    int bins() const {
+        int32_t n = 0;
+        check(crlot_beamformer_info(b_, nullptr, nullptr, &n, nullptr, nullptr, nullptr, nullptr), "crlot_beamformer_info");
+        return n;
+    }
+    int64_t frames() const {
+        int64_t n = 0;
+        check(crlot_beamformer_info(b_, nullptr, nullptr, nullptr, &n, nullptr, nullptr, nullptr), "crlot_beamformer_info");
+        return n;
+    }
+    // device blocks: the state [groups][2][M M][bins] floats, the weights and the steering
+    // vectors [groups][M][bins] float pairs
+    float* state() {
+        float* p = nullptr;
+        check(crlot_beamformer_state(b_, &p), "crlot_beamformer_state");
+        return p;
+    }
+    float* weights() {
+        float* p = nullptr;
+        check(crlot_beamformer_weights(b_, &p), "crlot_beamformer_weights");
+        return p;
+    }
+    float* steering() {
+        float* p = nullptr;
+        check(crlot_beamformer_steering(b_, &p), "crlot_beamformer_steering");
+        return p;
+    }
+    crlot_beamform_launch last_launch() const {
+        crlot_beamform_launch r{};
+        check(crlot_beamformer_last_launch(b_, &r), "crlot_beamformer_last_launch");
+        return r;
+    }
+    // spectra of stream g M + m as crlot_stft lays them out; d_mask null: 1 (targets 1, 2), ld_mask 0: shared;
+    // carry: continue from and advance the state (d_state_out may be null), else fresh into d_state_out
+    void accumulate_device(const float* d_spec, int64_t ld_spec, int64_t ldf_spec, const float* d_mask, int64_t ld_mask,
+                           int64_t ldf_mask, int n_groups, int64_t F, int target, bool carry, float* d_state_out,
+                           hipStream_t s = nullptr) {
+        check(crlot_beamform_accumulate(b_, d_spec, ld_spec, ldf_spec, d_mask, ld_mask, ldf_mask, n_groups, F, target,
+                                        carry ? 1 : 0, d_state_out, s),
+              "crlot_beamform_accumulate");
+    }
+    // null blocks: the object's
+    void solve_device(const float* d_state, const float* d_steer, int n_groups, float* d_w, hipStream_t s = nullptr) {
+        check(crlot_beamform_solve(b_, d_state, d_steer, n_groups, d_w, s), "crlot_beamform_solve");
+    }
+    void apply_device(const float* d_spec, int64_t ld_spec, int64_t ldf_spec, const float* d_w, int n_groups, int64_t F,
+                      float* d_out, int64_t ld_out, int64_t ldf_out, hipStream_t s = nullptr) {
+        check(crlot_beamform_apply(b_, d_spec, ld_spec, ldf_spec, d_w, n_groups, F, d_out, ld_out, ldf_out, s),
+              "crlot_beamform_apply");
+    }
+    // stft -> accumulate -> solve -> apply -> istft_ola, everything between in the plan's scratch
+    void beamform_device(const float* d_x, int64_t ld_x, const float* d_mask, int64_t ld_mask, int64_t ldf_mask,
+                         float* d_y, int64_t ld_y, int n_groups, int64_t T, hipStream_t s = nullptr) {
+        check(crlot_beamform(b_, d_x, ld_x, d_mask, ld_mask, ldf_mask, d_y, ld_y, n_groups, T, s), "crlot_beamform");
+    }
+    // one hop of the per-hop chain between the analysis half of st_in and the synthesis half of st_out;
+    // returns the samples per channel written to d_hop_out (0 or the hop size)
+    int hop_device(crlot_stream* st_in, crlot_stream* st_out, const float* d_hop_in, const float* d_mask,
+                   int64_t ld_mask, float* d_hop_out, hipStream_t s = nullptr) {
+        int32_t emitted = 0;
+        check(crlot_stream_beamform_hop(st_in, st_out, b_, d_hop_in, d_mask, ld_mask, d_hop_out, &emitted, s),
+              "crlot_stream_beamform_hop");
+        return emitted;
+    }
+    crlot_beamformer* get() const { return b_; }
+
+   private:
+    crlot_beamformer* b_ = nullptr;
+};
+
 // Real-time per-hop streaming with hops in host memory (BASELINE config 4):
 // the resident kernel behind crlot_stream_rt_*.  push_hop copies one hop of
 // channels x H samples in ([H][C] interleaved PCM or [C][H]), returns the H
