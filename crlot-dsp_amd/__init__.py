@@ -169,6 +169,18 @@ class BeamformLaunch(C.Structure):
                 ("grid", C.c_int64 * 3)]
 
 
+class WpeDesc(C.Structure):
+    """crlot_wpe_desc (include/crlot_dsp.h)."""
+    _fields_ = [("mics", C.c_int32), ("taps", C.c_int32), ("delay", C.c_int32), ("iterations", C.c_int32),
+                ("alpha", C.c_double), ("loading", C.c_double), ("floor", C.c_double)]
+
+
+class WpeLaunch(C.Structure):
+    """crlot_wpe_launch (include/crlot_dsp.h): what a dereverberator's last call launched."""
+    _fields_ = [("n_kernels", C.c_int32), ("kernel", C.c_int32 * 4), ("reserved", C.c_int32),
+                ("grid", C.c_int64 * 4)]
+
+
 class FftDesc(C.Structure):
     """crlot_fft_desc (include/crlot_dsp.h)."""
     _fields_ = [("domain", C.c_int32), ("nfft", C.c_int32), ("device", C.c_int32)]
@@ -316,6 +328,24 @@ def lib():
         "crlot_beamform_apply": ([vp, vp, i64, i64, vp, i32, i64, vp, i64, i64, vp], C.c_int),
         "crlot_beamform": ([vp, vp, i64, vp, i64, i64, vp, i64, i32, i64, vp], C.c_int),
         "crlot_stream_beamform_hop": ([vp, vp, vp, vp, vp, i64, vp, C.POINTER(i32), vp], C.c_int),
+        "crlot_wpe_desc_default": ([C.POINTER(WpeDesc)], C.c_int),
+        "crlot_wpe_create": ([vp, C.POINTER(WpeDesc), i32, C.POINTER(vp)], C.c_int),
+        "crlot_wpe_destroy": ([vp], None),
+        "crlot_wpe_prepare": ([vp], C.c_int),
+        "crlot_wpe_reset": ([vp], C.c_int),
+        "crlot_wpe_info": ([vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32),
+                            C.POINTER(i32), C.POINTER(i64), fp, fp, fp], C.c_int),
+        "crlot_wpe_state": ([vp, C.POINTER(vp)], C.c_int),
+        "crlot_wpe_inv_cov": ([vp, C.POINTER(vp)], C.c_int),
+        "crlot_wpe_taps": ([vp, C.POINTER(vp)], C.c_int),
+        "crlot_wpe_last_launch": ([vp, C.POINTER(WpeLaunch)], C.c_int),
+        "crlot_wpe_power": ([vp, vp, i64, i64, i32, i64, i64, vp, i64, i64, vp], C.c_int),
+        "crlot_wpe_accumulate": ([vp, vp, i64, i64, vp, i64, i64, i32, i64, i64, i32, vp, vp], C.c_int),
+        "crlot_wpe_solve": ([vp, vp, i32, vp, vp], C.c_int),
+        "crlot_wpe_filter": ([vp, vp, i64, i64, vp, i32, i64, i64, vp, i64, i64, vp], C.c_int),
+        "crlot_wpe_rls": ([vp, vp, i64, i64, i64, i64, vp, i64, i64, vp], C.c_int),
+        "crlot_wpe": ([vp, vp, i64, vp, i64, i32, i64, vp], C.c_int),
+        "crlot_stream_wpe_hop": ([vp, vp, vp, vp, vp, C.POINTER(i32), vp], C.c_int),
         "crlot_resample_geometry": ([C.POINTER(ResamplerDesc), C.POINTER(ResamplerGeometry)], C.c_int),
         "crlot_resample_table_host": ([C.POINTER(ResamplerDesc), fp], C.c_int),
         "crlot_rational_approx": ([C.c_double, i32, C.POINTER(i32), C.POINTER(i32)], C.c_int),
@@ -2672,6 +2702,312 @@ class Beamformer:
         s = _stream_handle(hop) if stream is None else stream
         _check(lib().crlot_stream_beamform_hop(st_in._h, st_out._h, self._h, hop.data_ptr(), mp, ldm, out.data_ptr(),
                                                C.byref(em), s), "crlot_stream_beamform_hop")
+        return out, em.value
+
+
+# ----------------------------------------------------------------- dereverberation
+class Dereverberator:
+    """The WPE dereverberator (crlot_wpe_create): `groups` independent arrays of `mics`
+    microphones (1..8), `taps` prediction taps (1..16, mics x taps <= 64) behind `delay`
+    frames (1..8).  Spectra are (G, M, F, N/2+1) complex64 in Plan.stft's layout; every
+    method that walks frames takes the run [f0, f1) of a tensor holding frames 0 .. f1-1.
+    power gives the inverse power rows, accumulate the correlation statistics, solve the
+    taps, filter the estimate, rls the recursive form on this object's inverse correlation
+    matrix and taps, dereverb runs stft -> iterations x (power, accumulate, solve, filter) ->
+    istft_ola on signals, hop is the per-hop chain.  Creation checks the descriptor
+    (ValueError) and touches no device."""
+
+    def __init__(self, plan: "Plan", mics: int, taps: int = 10, delay: int = 3, groups: int = 1, iterations: int = 3,
+                 alpha: float = 0.9999, loading: float = 1e-3, floor: float = 1e-10):
+        self._h = None
+        self.plan, self.mics, self.taps_count, self.delay = plan, int(mics), int(taps), int(delay)
+        self.groups, self.iterations = int(groups), int(iterations)
+        self.alpha, self.loading, self.floor = float(alpha), float(loading), float(floor)
+        self.bins = plan.frame_size // 2 + 1
+        self.stack = self.mics * self.taps_count
+        d = WpeDesc(self.mics, self.taps_count, self.delay, self.iterations, self.alpha, self.loading, self.floor)
+        h = C.c_void_p()
+        _check(lib().crlot_wpe_create(plan._h, C.byref(d), self.groups, C.byref(h)), "crlot_wpe_create")
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().crlot_wpe_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # interpreter shutdown
+            pass
+
+    def _info(self):
+        i = [C.c_int32() for _ in range(6)]
+        fr = C.c_int64()
+        f = [C.c_float() for _ in range(3)]
+        _check(lib().crlot_wpe_info(self._h, *[C.byref(v) for v in i], C.byref(fr), *[C.byref(v) for v in f]),
+               "crlot_wpe_info")
+        names = ("groups", "mics", "taps", "delay", "iterations", "bins")
+        out = {n: v.value for n, v in zip(names, i)}
+        out.update(frames=fr.value, alpha=f[0].value, loading=f[1].value, floor=f[2].value)
+        return out
+
+    @property
+    def frames(self) -> int:
+        """Frames the carried state (accumulate with carry, rls, hop) has seen since create / reset."""
+        return self._info()["frames"]
+
+    @property
+    def state_planes(self) -> int:
+        return self.stack * self.stack + 2 * self.stack * self.mics
+
+    def prepare(self):
+        with _torch().cuda.device(self.plan._device_index()):
+            _check(lib().crlot_wpe_prepare(self._h), "crlot_wpe_prepare")
+
+    def reset(self):
+        """Zero the state, the ring, the taps and the frame counter; the inverse correlation matrix back to the identity."""
+        _check(lib().crlot_wpe_reset(self._h), "crlot_wpe_reset")
+
+    def _view(self, fn, name, shape, cplx):
+        torch = _torch()
+        ptr = C.c_void_p()
+        dev = self.plan._device_index()
+        with torch.cuda.device(dev):
+            _check(fn(self._h, C.byref(ptr)), name)
+            t = torch.as_tensor(_DeviceFloats(ptr.value, shape + ((2,) if cplx else ())), device=f"cuda:{dev}")
+        return torch.view_as_complex(t) if cplx else t
+
+    def state(self):
+        """The carried statistics, a (groups, L L + 2 L M, N/2+1) float32 torch view: R as a
+        Hermitian matrix (the L diagonals, then Re, Im of every i < j), then P as Re, Im, l-major."""
+        return self._view(lib().crlot_wpe_state, "crlot_wpe_state", (self.groups, self.state_planes, self.bins), False)
+
+    def inv_cov(self):
+        """The RLS step's inverse correlation matrix, a (groups, L L, N/2+1) float32 torch view."""
+        return self._view(lib().crlot_wpe_inv_cov, "crlot_wpe_inv_cov", (self.groups, self.stack * self.stack, self.bins),
+                          False)
+
+    def taps(self):
+        """The object's taps, a (groups, L, M, N/2+1) complex64 torch view."""
+        return self._view(lib().crlot_wpe_taps, "crlot_wpe_taps", (self.groups, self.stack, self.mics, self.bins), True)
+
+    def set_taps(self, g):
+        """Replace the object's taps: (groups, L, M, N/2+1) or (L, M, N/2+1) complex64, host or device."""
+        torch = _torch()
+        view = self.taps()
+        v = torch.as_tensor(np.ascontiguousarray(g, np.complex64)) if not torch.is_tensor(g) else g
+        if v.dtype != torch.complex64:
+            raise ValueError("taps must be complex64")
+        if tuple(v.shape) == tuple(view.shape[1:]):
+            v = v[None].expand(self.groups, -1, -1, -1)
+        if tuple(v.shape) != tuple(view.shape):
+            raise ValueError(f"taps must be {tuple(view.shape)} or {tuple(view.shape[1:])}")
+        view.copy_(v.to(view.device))
+
+    def last_launch(self) -> dict:
+        r = WpeLaunch()
+        _check(lib().crlot_wpe_last_launch(self._h, C.byref(r)), "crlot_wpe_last_launch")
+        kernels = [int(r.kernel[i]) for i in range(r.n_kernels)]
+        return {"kernels": kernels, "names": [kernel_name(k) for k in kernels],
+                "grids": [int(r.grid[i]) for i in range(r.n_kernels)]}
+
+    def _spec(self, spec, what="spec"):
+        if len(spec.shape) == 3:
+            spec = spec[None]
+        G, F, ld, ldf = _bf_spec_layout(*_tensor_layout(spec), self.plan._device_index(), self.mics, self.bins, what)
+        return spec, G, F, ld, ldf
+
+    def _run(self, F, f0, f1):
+        f1 = F if f1 is None else int(f1)
+        f0 = int(f0)
+        if not 0 <= f0 <= f1 <= F:
+            raise ValueError(f"the run [f0, f1) must lie within the {F} frames given")
+        return f0, f1
+
+    def _block(self, t, shape, dtype, what):
+        tshape, _, tdtype, dev = _tensor_layout(t)
+        if tshape != tuple(shape) or tdtype != dtype or not t.is_contiguous():
+            raise ValueError(f"{what} must be a contiguous {tuple(shape)} {dtype} tensor")
+        if dev is None or dev != self.plan._device_index():
+            raise ValueError(f"{what} must live on the plan's device")
+        return t.data_ptr()
+
+    def _pow_layout(self, pw, G, F):
+        shape, strides, dtype, dev = _tensor_layout(pw)
+        if shape != (G, F, self.bins) or dtype != "float32" or dev is None or dev != self.plan._device_index():
+            raise ValueError(f"power rows must be a ({G}, {F}, {self.bins}) float32 tensor on the plan's device")
+        if strides[2] != 1:
+            raise ValueError("power rows must be contiguous")
+        ldf = strides[1] if F > 1 else self.bins
+        ld = strides[0] if G > 1 else F * ldf
+        if ldf < self.bins or ld < (F - 1) * ldf + self.bins:
+            raise ValueError("power rows overlap")
+        return int(ld), int(ldf)
+
+    def power(self, z, f0: int = 0, f1=None, out=None, stream: int | None = None):
+        """z: (G, M, F, N/2+1) -> the inverse power rows (G, F, N/2+1) float32 of the frames [f0, f1)
+        (rows outside the run are left as they are; a fresh `out` is zeroed)."""
+        torch = _torch()
+        z, G, F, ld, ldf = self._spec(z, "z")
+        f0, f1 = self._run(F, f0, f1)
+        if out is None:
+            out = torch.zeros((G, F, self.bins), dtype=torch.float32, device=z.device)
+        ldp, ldfp = self._pow_layout(out, G, F)
+        if _tensors_overlap(out, z):
+            raise ValueError("out overlaps the spectra")
+        s = _stream_handle(z) if stream is None else stream
+        _check(lib().crlot_wpe_power(self._h, z.data_ptr(), ld, ldf, G, f0, f1, out.data_ptr(), ldp, ldfp, s),
+               "crlot_wpe_power")
+        return out
+
+    def accumulate(self, spec, power, f0: int = 0, f1=None, carry: bool = False, state_out=None,
+                   stream: int | None = None):
+        """The statistics of the frames [f0, f1) of spec under the inverse power rows `power`
+        ((G, F, N/2+1) float32).  carry=False: fresh state, any G, the result in state_out
+        (allocated zeroed when None), this object untouched.  carry=True: G must be the group
+        count; the run continues from this object's state and advances it.  Returns the
+        (G, L L + 2 L M, N/2+1) state the run ends with."""
+        torch = _torch()
+        spec, G, F, ld, ldf = self._spec(spec)
+        f0, f1 = self._run(F, f0, f1)
+        ldp, ldfp = self._pow_layout(power, G, F)
+        if carry and G != self.groups:
+            raise ValueError(f"carry needs {self.groups} groups, not {G}")
+        out = state_out
+        if out is None and not carry:
+            out = torch.zeros((G, self.state_planes, self.bins), dtype=torch.float32, device=spec.device)
+        op = None
+        if out is not None:
+            op = self._block(out, (G, self.state_planes, self.bins), "float32", "state_out")
+            if _tensors_overlap(out, spec) or _tensors_overlap(out, power):
+                raise ValueError("state_out overlaps an input")
+        s = _stream_handle(spec) if stream is None else stream
+        _check(lib().crlot_wpe_accumulate(self._h, spec.data_ptr(), ld, ldf, power.data_ptr(), ldp, ldfp, G, f0, f1,
+                                          int(bool(carry)), op, s), "crlot_wpe_accumulate")
+        return self.state() if out is None else out
+
+    def solve(self, state=None, taps=None, stream: int | None = None):
+        """The taps of a state block (None: this object's); taps (None: this object's, which is
+        returned) is a (G, L, M, N/2+1) complex64 device tensor.  G may not exceed the group count."""
+        G = self.groups if state is None else int(state.shape[0])
+        if taps is not None and state is None:
+            G = int(taps.shape[0])
+        sp = None if state is None else self._block(state, (G, self.state_planes, self.bins), "float32", "state")
+        tp = None if taps is None else self._block(taps, (G, self.stack, self.mics, self.bins), "complex64", "taps")
+        if (state is None or taps is None) and G != self.groups:
+            raise ValueError(f"this object's blocks need {self.groups} groups, not {G}")
+        if G > self.groups:
+            raise ValueError(f"solve runs in this object's workspace: at most {self.groups} groups, not {G}")
+        if state is not None and taps is not None and _tensors_overlap(state, taps):
+            raise ValueError("taps overlap the state")
+        like = state if state is not None else taps
+        s = stream if stream is not None else _stream_handle(like if like is not None else self.state())
+        with _torch().cuda.device(self.plan._device_index()):
+            _check(lib().crlot_wpe_solve(self._h, sp, G, tp, s), "crlot_wpe_solve")
+        return self.taps() if taps is None else taps
+
+    def _out(self, spec, G, F, out):
+        torch = _torch()
+        if out is None:
+            out = torch.zeros((G, self.mics, F, self.bins), dtype=torch.complex64, device=spec.device)
+        o4 = out[None] if len(out.shape) == 3 else out
+        Go, Fo, ld_o, ldf_o = _bf_spec_layout(*_tensor_layout(o4), self.plan._device_index(), self.mics, self.bins, "out")
+        if (Go, Fo) != (G, F):
+            raise ValueError(f"out must hold {G} groups of {F} frames")
+        if _tensors_overlap(o4, spec):
+            raise ValueError("out overlaps the spectra")
+        return out, o4, ld_o, ldf_o
+
+    def filter(self, spec, taps=None, f0: int = 0, f1=None, out=None, stream: int | None = None):
+        """spec -> the estimate (G, M, F, N/2+1) complex64 of the frames [f0, f1) with `taps` (None:
+        this object's); frames outside the run are left as they are (a fresh `out` is zeroed)."""
+        squeeze = len(spec.shape) == 3
+        spec, G, F, ld, ldf = self._spec(spec)
+        f0, f1 = self._run(F, f0, f1)
+        tp = None if taps is None else self._block(taps, (G, self.stack, self.mics, self.bins), "complex64", "taps")
+        if taps is None and G != self.groups:
+            raise ValueError(f"this object's taps need {self.groups} groups, not {G}")
+        out, o4, ld_o, ldf_o = self._out(spec, G, F, out)
+        if taps is not None and _tensors_overlap(o4, taps):
+            raise ValueError("out overlaps the taps")
+        s = _stream_handle(spec) if stream is None else stream
+        _check(lib().crlot_wpe_filter(self._h, spec.data_ptr(), ld, ldf, tp, G, f0, f1, o4.data_ptr(), ld_o, ldf_o, s),
+               "crlot_wpe_filter")
+        return o4[0] if squeeze and len(out.shape) == 4 else out
+
+    def rls(self, spec, f0: int = 0, f1=None, out=None, stream: int | None = None):
+        """The recursive step over the frames [f0, f1) on this object's inverse correlation matrix
+        and taps; spec must have the object's group count.  Returns the predictions (G, M, F,
+        N/2+1) complex64 (frames outside the run as filter leaves them)."""
+        squeeze = len(spec.shape) == 3
+        spec, G, F, ld, ldf = self._spec(spec)
+        if G != self.groups:
+            raise ValueError(f"rls needs {self.groups} groups, not {G}")
+        f0, f1 = self._run(F, f0, f1)
+        out, o4, ld_o, ldf_o = self._out(spec, G, F, out)
+        s = _stream_handle(spec) if stream is None else stream
+        _check(lib().crlot_wpe_rls(self._h, spec.data_ptr(), ld, ldf, f0, f1, o4.data_ptr(), ld_o, ldf_o, s),
+               "crlot_wpe_rls")
+        return o4[0] if squeeze and len(out.shape) == 4 else out
+
+    def dereverb(self, x, y=None, stream: int | None = None):
+        """x: (G, M, T) or (M, T) float32 device tensor -> y: (G, M, F H): istft_ola of `iterations`
+        rounds of filter(solve(accumulate(power))) on stft(x), bit for bit, everything between
+        in the plan's scratch; this object is untouched.  The plan must have no stored
+        spectral mask."""
+        torch = _torch()
+        squeeze = x.dim() == 2
+        if squeeze:
+            x = x[None]
+        shape, strides, dtype, dev = _tensor_layout(x)
+        if len(shape) != 3 or shape[1] != self.mics or dtype != "float32" or dev is None:
+            raise ValueError(f"x must be a (G, {self.mics}, T) or ({self.mics}, T) float32 device tensor")
+        if dev != self.plan._device_index():
+            raise ValueError(f"x must live on the plan's device {self.plan._device_index()}")
+        G, T = int(shape[0]), int(shape[2])
+        if T > 1 and strides[2] != 1:
+            raise ValueError("x must have contiguous rows")
+        ld_x = int(strides[1]) if self.mics > 1 else max(int(strides[1]), T)
+        if ld_x < T or (G > 1 and int(strides[0]) != self.mics * ld_x):
+            raise ValueError(f"x: rows overlap, or the groups are not {self.mics} microphone strides apart")
+        if getattr(self.plan, "_mask", None) is not None:
+            raise ValueError("dereverb: the plan has a stored spectral mask; clear it first")
+        Ly = self.plan.frame_count(T) * self.plan.hop_size
+        if y is None:
+            y = torch.empty((G, self.mics, Ly), dtype=x.dtype, device=x.device)
+        y3 = y[None] if y.dim() == 2 else y
+        if tuple(y3.shape[:2]) != (G, self.mics) or not y3.is_contiguous():
+            raise ValueError(f"y must be a contiguous ({G}, {self.mics}, >= {Ly}) float32 tensor")
+        ld_y = _gl_y_layout(*_tensor_layout(y3.reshape(G * self.mics, -1)), dev, G * self.mics, Ly)
+        if _tensors_overlap(y3, x):
+            raise ValueError("y overlaps the input")
+        s = _stream_handle(x) if stream is None else stream
+        _check(lib().crlot_wpe(self._h, x.data_ptr(), ld_x, y3.data_ptr(), ld_y, G, T, s), "crlot_wpe")
+        return y3[0] if squeeze and y.dim() == 3 else y
+
+    def hop(self, st_in: "Stream", st_out: "Stream", hop, out=None, stream: int | None = None) -> tuple:
+        """One hop of the per-hop chain (crlot_stream_wpe_hop): st_in (its analysis half) and
+        st_out (its synthesis half) are Streams of groups x mics channels on this object's
+        plan; hop as st_in.stft_hop's.  The inverse correlation matrix and the taps advance by
+        one frame.  Returns (out, emitted): out as st_out's hops, written when emitted is H."""
+        torch = _torch()
+        if not isinstance(st_in, Stream) or not isinstance(st_out, Stream):
+            raise ValueError("st_in and st_out must be Stream objects")
+        if st_in.plan is not self.plan or st_out.plan is not self.plan:
+            raise ValueError("the streams must be on the dereverberator's plan")
+        C_ = self.groups * self.mics
+        if st_in.channels != C_ or st_out.channels != C_:
+            raise ValueError(f"st_in and st_out need {C_} channels each")
+        hop = st_in._hop_arg(hop)
+        H = self.plan.hop_size
+        if out is None:
+            out = torch.empty((H, C_) if st_out.interleaved else (C_, H), dtype=torch.float32, device=hop.device)
+        st_out._hop_arg(out, "out")
+        em = C.c_int32()
+        s = _stream_handle(hop) if stream is None else stream
+        _check(lib().crlot_stream_wpe_hop(st_in._h, st_out._h, self._h, hop.data_ptr(), out.data_ptr(), C.byref(em), s),
+               "crlot_stream_wpe_hop")
         return out, em.value
 
 

@@ -200,6 +200,12 @@ extern "C" const char* crlot_kernel_name(int32_t id) {
         case CRLOT_K_BF_SOLVE: return "k_bf_solve";
         case CRLOT_K_BF_APPLY: return "k_bf_apply";
         case CRLOT_K_BF_HOP: return "k_bf_hop";
+        case CRLOT_K_WPE_POWER: return "k_wpe_power";
+        case CRLOT_K_WPE_ACC: return "k_wpe_acc";
+        case CRLOT_K_WPE_SOLVE: return "k_wpe_solve";
+        case CRLOT_K_WPE_FILTER: return "k_wpe_filter";
+        case CRLOT_K_WPE_GAIN: return "k_wpe_gain";
+        case CRLOT_K_WPE_UPDATE: return "k_wpe_update";
         case CRLOT_K_EXPERIMENT: return "k_experiment";
         default: return "unknown";
     }

@@ -8,6 +8,7 @@
 #include <cstring>
 
 #include "beamform_launch.h"
+#include "wpe_launch.h"
 #include "plan_internal.h"
 
 using namespace crlot;
@@ -384,6 +385,64 @@ int crlot_stream_beamform_hop(crlot_stream* st_in, crlot_stream* st_out, crlot_b
         if (emitted) *emitted = int32_t(H);
     }
     crlot::beamformer_set_last(bf, rec);
+    return CRLOT_OK;
+}
+
+// One hop of the dereverberation chain (the contract is in include/crlot_dsp.h,
+// "dereverberation"): the analysis half of st_in into the object's ring of delay + taps
+// rows per channel, the two kernels of the RLS step on its inverse correlation matrix and
+// taps, the synthesis half of st_out from its prediction rows.
+int crlot_stream_wpe_hop(crlot_stream* st_in, crlot_stream* st_out, crlot_dereverberator* wpe, const float* d_in, float* d_out,
+                         int32_t* emitted, void* stream) {
+    if (emitted) *emitted = 0;
+    if (!st_in || !st_out) return fail(CRLOT_EINVAL, "null stream");
+    if (!wpe) return fail(CRLOT_EINVAL, "null wpe object");
+    if (!d_in || !d_out) return fail(CRLOT_EINVAL, "null buffer");
+    if (st_in == st_out) return fail(CRLOT_EINVAL, "the two halves need a stream object each");
+    crlot::WpeHopView v{};
+    crlot::wpe_hop_shape(wpe, &v);  // (the object's block is allocated once every check has passed)
+    crlot_plan* p = st_in->plan;
+    if (v.plan != p || st_out->plan != p) return fail(CRLOT_EINVAL, "the wpe object and the streams must share one plan");
+    if (st_in->channels != int64_t(v.groups) * v.mics || st_out->channels != st_in->channels)
+        return fail(CRLOT_EINVAL, "both streams must have groups x mics channels");
+    const int64_t H = p->geo.h, done = drop_frames_after(st_in->q, p->geo.n, H);
+    if (v.frames != done || st_out->kf != done || (st_in->mode == 2 && st_in->kf != 0) ||
+        (st_out->mode == 2 && st_out->q != 0))
+        return fail(CRLOT_ERUNTIME, "the wpe object's and the streams' frame counters differ; reset all three");
+    if (int rc = stream_enter(st_in, 2)) return rc;
+    if (int rc = stream_enter(st_out, 2)) return rc;
+    if (int rc = crlot::wpe_hop_view(wpe, &v)) return rc;
+    DeviceGuard g(p->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int64_t row = int64_t(p->geo.n) + 2;
+    const int64_t k = stream_frame_of_hop(st_in, st_in->q);
+    crlot_wpe_launch rec{};
+    const auto hop_grid = [](const crlot_stream* st) { return st->any ? int64_t(0) : (int64_t(st->channels) + 3) / 4; };
+    const int64_t C = st_in->channels;
+    const int64_t ld = st_in->interleaved ? 1 : H, inc = st_in->interleaved ? C : 1;
+    {
+        // frame k of channel c goes to row k mod ring of the channel's ring
+        float* at = v.d_ring + (k >= 0 ? k % v.ring : 0) * row;
+        hipError_t e = crlot::launch_stream_stft_hop(p->geo, tables(p), p->d_twany, st_in->any, d_in, ld, inc, at,
+                                                     v.ring * row, st_in->d_hist, st_in->channels, st_in->q, k, s);
+        if (e != hipSuccess) return hip_fail(e, "stream kernel launch");
+        rec.n_kernels = 1;
+        rec.kernel[0] = CRLOT_K_STREAM_STFT;
+        rec.grid[0] = hop_grid(st_in);
+    }
+    st_in->q += 1;
+    if (k >= 0) {
+        if (int rc = crlot::wpe_hop_run(wpe, k, &rec, s)) return rc;
+        const int64_t ldo = st_out->interleaved ? 1 : H, inco = st_out->interleaved ? C : 1;
+        hipError_t e = crlot::launch_stream_istft_hop(p->geo, tables(p), p->d_twany, st_out->any, v.d_pred, row, nullptr,
+                                                      0, d_out, ldo, inco, st_out->d_acc, st_out->channels, st_out->kf, s);
+        if (e != hipSuccess) return hip_fail(e, "stream kernel launch");
+        st_out->kf += 1;
+        rec.kernel[rec.n_kernels] = CRLOT_K_STREAM_ISTFT;
+        rec.grid[rec.n_kernels++] = hop_grid(st_out);
+        if (emitted) *emitted = int32_t(H);
+    }
+    crlot::wpe_set_last(wpe, rec);
     return CRLOT_OK;
 }
 

@@ -283,6 +283,12 @@ int crlot_test_inject(int32_t what, int32_t count);
 #define CRLOT_K_BF_SOLVE 61     /* crlot_beamform_solve: loading, Cholesky and the MVDR weights of a bin in registers */
 #define CRLOT_K_BF_APPLY 62     /* crlot_beamform_apply: y = w^H x per frame, the weights of a bin in registers */
 #define CRLOT_K_BF_HOP 63       /* crlot_stream_beamform_hop: one frame's update, the solve when due and the apply */
+#define CRLOT_K_WPE_POWER 64    /* crlot_wpe_power: the inverse power row of a group's frames, a lane per column */
+#define CRLOT_K_WPE_ACC 65      /* crlot_wpe_accumulate: the stacked correlation matrices per bin, a lane per 4 x 4 tile */
+#define CRLOT_K_WPE_SOLVE 66    /* crlot_wpe_solve: loading, Cholesky and the taps of a bin, in place on workspace planes */
+#define CRLOT_K_WPE_FILTER 67   /* crlot_wpe_filter: the prediction filter along the frames, a lane per (column, microphone) */
+#define CRLOT_K_WPE_GAIN 68     /* crlot_wpe_rls: v = Q y~ of one frame, a wave per row of Q */
+#define CRLOT_K_WPE_UPDATE 69   /* crlot_wpe_rls: the update of Q by rows, the prediction and the taps' update */
 #define CRLOT_K_EXPERIMENT 99   /* experiment builds only */
 typedef struct crlot_launch_info {
     int32_t n_kernels;
@@ -1522,6 +1528,156 @@ int crlot_beamform(crlot_beamformer* bf, const float* d_x, int64_t ld_x, const f
                    int64_t ldf_mask, float* d_y, int64_t ld_y, int32_t n_groups, int64_t T, void* stream);
 int crlot_stream_beamform_hop(crlot_stream* st_in, crlot_stream* st_out, crlot_beamformer* bf, const float* d_hop_in,
                               const float* d_mask, int64_t ld_mask, float* d_hop_out, int32_t* emitted, void* stream);
+
+/* ---------------------------------------------------------------- dereverberation
+ * Weighted prediction error (WPE; Nakatani et al. 2010, Yoshioka & Nakatani 2012; the
+ * recursive form as nara_wpe's OnlineWPE): G independent groups of M microphones, the late
+ * reverberation predicted from K delayed frames of all M spectra and subtracted.  The
+ * input is spectra in crlot_stft's layout, the output M spectra per group in the same
+ * layout, which is what crlot_beamform_accumulate / crlot_stream_beamform_hop and
+ * crlot_istft_ola take.  The reference project has no dereverberation: nothing in this
+ * section restates it, and no entry below cites it.
+ *
+ * Terms.  1 <= M <= 8 microphones, 1 <= K <= 16 taps, L = M K <= 64, delay 1 <= D <= 8.
+ * Stream g M + m is microphone m of group g.  Frame t of stream s is at d_spec + s ld_spec +
+ * t ldf_spec, N/2+1 float pairs; a frame before the start of the signal (t < 0) is a row of
+ * zeros.  The stacked vector y~(t) of a (group, bin) has L entries, entry l = tau M + m
+ * (tau = 0 .. K-1) equal to Y_m(t - D - tau).  Every entry below that walks frames takes the
+ * half-open run [f0, f1) of a buffer that holds frames 0 .. f1-1: cut and carry is two
+ * calls on the same buffer.
+ *
+ * Values.  float32, every product, sum, difference and quotient rounded on its own (no
+ * FMA), division and sqrtf correctly rounded; max(a, b) is a > b ? a : b; tiny = 1e-30f; the
+ * three complex products as the beamformer's section words them; |z|^2 = (re re) + (im im).
+ *   1  power.  p = |Z_0|^2, then + |Z_m|^2 in m order; lambda = max(p / float(M), floor_f32);
+ *      iota = 1 / lambda.  Z is the observation on the first iteration and the previous
+ *      iteration's estimate afterwards.  The stored row is iota: group g, frame t, bin b at
+ *      d_pow[g ld_pow + t ldf_pow + b].
+ *   2  accumulate (Welch sums only), frames in order, every plane S = S + (iota T).  R_ij
+ *      averages y~_i conj(y~_j): the diagonal T = (re re) + (im im); i < j: T = y~_i conj(y~_j).
+ *      P_lm averages y~_l conj(Y_m(t)) by the same product.  The state block is
+ *      [group][L L + 2 L M][N/2+1]: R as the beamformer stores a Hermitian matrix (the L
+ *      diagonals, then Re, Im of every i < j in lexicographic order), then P as Re, Im
+ *      planes, l-major (plane L L + 2 (l M + m)).  All 0 after create / reset.
+ *   3  solve.  tr = R_00, then + R_ll in order; ld = max(loading_f32 (tr / float(L)), tiny);
+ *      A = R + ld I; Cholesky, forward and back substitution exactly as the beamformer's
+ *      step 3 words them with M replaced by L; one solve per column m of P (m ascending;
+ *      the columns are independent) gives the taps G = A^-1 P, a block [group][L][M][N/2+1]
+ *      float pairs, zero after create / reset (the filter then passes Y through).  No term
+ *      of this step starts from a literal zero.
+ *   4  filter.  acc = (0, 0); for l ascending acc = acc + conj(G_lm) y~_l(t) per component;
+ *      X_m(t) = Y_m(t) - acc per component.  The imaginary parts of DC and Nyquist are stored
+ *      as computed.
+ *   5  RLS step for frame t.  Q (the inverse correlation matrix, Hermitian, L L planes as R)
+ *      is the identity and the taps zero after create / reset.  pred_m by step 4 with the
+ *      old taps: this is the output.  lambda by step 1 on Y(t).  v_i = sum over j of Q_ij y~_j,
+ *      starting from j = 0's term and adding j = 1 .. in order; for i > j the conjugate of
+ *      the stored entry (conj(Q_ji) y~_j), for i < j Q_ij y~_j, the diagonal term (q y.re,
+ *      q y.im).  s = (y~_0.re v_0.re) + (y~_0.im v_0.im), then + the same of i = 1 .. in order;
+ *      den = max((alpha_f32 lambda) + s, tiny); k_i = v_i / den per component; Q_ij = (Q_ij -
+ *      k_i conj(v_j)) / alpha_f32 for i < j per component, Q_ii = (Q_ii - ((k_i.re v_i.re) +
+ *      (k_i.im v_i.im))) / alpha_f32; G_lm = G_lm + k_l conj(pred_m).
+ * Orders this contract fixes where the proposal left them open: the stored power row is
+ * iota, not lambda; v and s start from their first term, not from zero; Q's lower triangle
+ * is never stored or updated.  Output bits do not depend on the grid, the group count, a
+ * group's position, the leading dimensions, where a run along the frame axis is cut, or
+ * how matrix entries are spread over lanes, waves or launches.
+ *
+ * loading (default 1e-3) is relative to trace / L.  With 1e-3 the condition number of A
+ * stays within float32's reach (3e4 on a reverberant test scene); 1e-6 does not (2e7):
+ * keep the default unless the statistics are known to be well conditioned.
+ *
+ * crlot_wpe_create(plan, desc, groups, out) touches no device.  The descriptor is checked
+ * first, with no plan needed: mics outside 1..8, taps outside 1..16, mics taps > 64, delay
+ * outside 1..8, iterations outside 1..10, alpha NaN or outside (0, 1], loading NaN / Inf /
+ * < 0, floor NaN / Inf / <= 0 are CRLOT_EINVAL; then a null argument, groups < 1, a size or
+ * grid that does not fit.  prepare, or the first call that needs it, makes one
+ * allocation: the state, Q, the taps, the v rows, the solve's workspace, and the ring and
+ * the prediction rows of the per-hop entry (which forms its power inline).  _state, _inv_cov and _taps
+ * return device pointers the caller may read and write; _reset synchronises the device,
+ * zeroes the state, the ring, the taps and the frame counter and sets Q to the identity.
+ * A single-owner object like crlot_stream; graph capture is not supported.
+ *
+ * crlot_wpe_power(wpe, d_z, ld_z, ldf_z, n_groups, f0, f1, d_pow, ld_pow, ldf_pow, stream):
+ * step 1 (CRLOT_K_WPE_POWER).  crlot_wpe_accumulate(wpe, d_spec, ld_spec, ldf_spec, d_pow,
+ * ld_pow, ldf_pow, n_groups, f0, f1, carry, d_state_out, stream): step 2 (CRLOT_K_WPE_ACC).
+ * carry = 0: every group starts from zero, any n_groups, the result goes to d_state_out
+ * (required), the object is untouched.  carry = 1: n_groups must equal the object's; the
+ * run continues from the object's state and advances its frame counter; d_state_out may
+ * be NULL (else it receives a copy).  crlot_wpe_solve(wpe, d_state, n_groups, d_taps,
+ * stream): step 3 (CRLOT_K_WPE_SOLVE) in the object's workspace, so n_groups may not exceed
+ * the object's; NULL for a block means the object's (then n_groups must equal the
+ * object's).  crlot_wpe_filter(wpe, d_spec, ld_spec, ldf_spec, d_taps, n_groups, f0, f1,
+ * d_out, ld_out, ldf_out, stream): step 4 (CRLOT_K_WPE_FILTER), frame t of stream s at d_out
+ * + s ld_out + t ldf_out.  crlot_wpe_rls(wpe, d_spec, ld_spec, ldf_spec, f0, f1, d_out, ld_out,
+ * ldf_out, stream): step 5 on the object's Q and taps for the object's group count, one
+ * CRLOT_K_WPE_GAIN and one CRLOT_K_WPE_UPDATE launch per frame, looped on the host; the
+ * frame counter advances.  n_groups of 0 or an empty run: CRLOT_OK, nothing written.
+ * CRLOT_EINVAL: null buffers, f0 < 0, a leading dimension too small or (spectra) odd,
+ * outputs that overlap an input, the state or the taps.
+ *
+ * crlot_wpe(wpe, d_x, ld_x, d_y, ld_y, n_groups, T, stream) = crlot_stft of the n_groups M
+ * signals (stream s at d_x + s ld_x) -> iterations x (power of the observation, then of the
+ * last estimate -> accumulate from zero -> solve -> filter) -> crlot_istft_ola of the
+ * n_groups M estimates (stream s at d_y + s ld_y, F H samples).  Everything between stays in
+ * the stream's sliced workspace, sliced by group; bit for bit the hand composition under
+ * either frame-pairing setting.  The object is untouched.  A plan that holds a stored
+ * spectral mask is CRLOT_EINVAL.
+ *
+ * crlot_stream_wpe_hop(st_in, st_out, wpe, d_hop_in, d_hop_out, emitted, stream): one hop of
+ * the per-hop chain.  Both streams have groups M channels and are in split mode on the
+ * object's plan (st_in's analysis half, st_out's synthesis half).  A hop =
+ * crlot_stream_stft_hop into the object's ring of D + K rows per channel -> gain -> update
+ * -> crlot_stream_istft_hop of the prediction rows: bit for bit stft_hop -> crlot_wpe_rls
+ * over that one frame -> istft_hop.  A hop that completes no frame runs only the analysis
+ * half, leaves d_hop_out untouched and sets *emitted = 0 (else the hop size).
+ * CRLOT_EINVAL: channel counts or plans that do not match; CRLOT_ERUNTIME: frame counters
+ * that differ (reset all three), a stream in whole-hop mode.  crlot_wpe_last_launch lists
+ * the last call's kernels and grids (crlot_wpe: the last iteration's four; crlot_wpe_rls:
+ * the last frame's two). */
+typedef struct crlot_wpe_desc {
+    int32_t mics;        /* M, 1..8 */
+    int32_t taps;        /* K, 1..16, M K <= 64 */
+    int32_t delay;       /* D, 1..8 */
+    int32_t iterations;  /* 1..10: crlot_wpe's passes (default 3) */
+    double alpha;        /* (0, 1]: the RLS forgetting factor (default 0.9999) */
+    double loading;      /* >= 0, finite: diagonal loading relative to trace / L (default 1e-3) */
+    double floor;        /* > 0, finite: the power floor (default 1e-10) */
+} crlot_wpe_desc;
+typedef struct crlot_dereverberator crlot_dereverberator;
+typedef struct crlot_wpe_launch {
+    int32_t n_kernels;  /* 0: no launch yet */
+    int32_t kernel[4];  /* CRLOT_K_* in launch order */
+    int32_t reserved;
+    int64_t grid[4];    /* workgroups of each */
+} crlot_wpe_launch;
+int crlot_wpe_desc_default(crlot_wpe_desc* d);
+int crlot_wpe_create(crlot_plan* plan, const crlot_wpe_desc* desc, int32_t groups, crlot_dereverberator** out);
+void crlot_wpe_destroy(crlot_dereverberator* wpe);
+int crlot_wpe_prepare(crlot_dereverberator* wpe);
+int crlot_wpe_reset(crlot_dereverberator* wpe);
+int crlot_wpe_info(const crlot_dereverberator* wpe, int32_t* groups, int32_t* mics, int32_t* taps, int32_t* delay,
+                   int32_t* iterations, int32_t* bins, int64_t* frames, float* alpha, float* loading, float* floor);
+int crlot_wpe_state(crlot_dereverberator* wpe, float** d_state /* [groups][L L + 2 L M][N/2+1] */);
+int crlot_wpe_inv_cov(crlot_dereverberator* wpe, float** d_q /* [groups][L L][N/2+1] */);
+int crlot_wpe_taps(crlot_dereverberator* wpe, float** d_taps /* [groups][L][M][N/2+1] float pairs */);
+int crlot_wpe_last_launch(const crlot_dereverberator* wpe, crlot_wpe_launch* out);
+int crlot_wpe_power(crlot_dereverberator* wpe, const float* d_z, int64_t ld_z, int64_t ldf_z, int32_t n_groups, int64_t f0,
+                    int64_t f1, float* d_pow, int64_t ld_pow, int64_t ldf_pow, void* stream);
+int crlot_wpe_accumulate(crlot_dereverberator* wpe, const float* d_spec, int64_t ld_spec, int64_t ldf_spec, const float* d_pow,
+                         int64_t ld_pow, int64_t ldf_pow, int32_t n_groups, int64_t f0, int64_t f1, int32_t carry,
+                         float* d_state_out /* carry = 1: may be NULL */, void* stream);
+int crlot_wpe_solve(crlot_dereverberator* wpe, const float* d_state /* NULL: the object's */, int32_t n_groups,
+                    float* d_taps /* NULL: the object's */, void* stream);
+int crlot_wpe_filter(crlot_dereverberator* wpe, const float* d_spec, int64_t ld_spec, int64_t ldf_spec,
+                     const float* d_taps /* NULL: the object's */, int32_t n_groups, int64_t f0, int64_t f1,
+                     float* d_out, int64_t ld_out, int64_t ldf_out, void* stream);
+int crlot_wpe_rls(crlot_dereverberator* wpe, const float* d_spec, int64_t ld_spec, int64_t ldf_spec, int64_t f0, int64_t f1,
+                  float* d_out, int64_t ld_out, int64_t ldf_out, void* stream);
+int crlot_wpe(crlot_dereverberator* wpe, const float* d_x, int64_t ld_x, float* d_y, int64_t ld_y, int32_t n_groups, int64_t T,
+              void* stream);
+int crlot_stream_wpe_hop(crlot_stream* st_in, crlot_stream* st_out, crlot_dereverberator* wpe, const float* d_hop_in,
+                         float* d_hop_out, int32_t* emitted, void* stream);
 
 /* host helpers (no device) */
 #define CRLOT_MEL_HTK 0

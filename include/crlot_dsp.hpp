@@ -847,6 +847,122 @@ class Beamformer {
     crlot_beamformer* b_ = nullptr;
 };
 
+// The WPE dereverberator (crlot_wpe_create): groups of 1..8 microphones, the late
+// reverberation predicted from `taps` frames behind `delay` and subtracted; offline in
+// `iterations` passes, or recursively per frame.  Every run of frames is [f0, f1) of a
+// buffer that holds frames 0 .. f1-1.  The plan (an StftEngine's plan()) must outlive the
+// object.
+class Dereverberator {
+   public:
+    Dereverberator(crlot_plan* plan, int mics, int taps = 10, int delay = 3, int groups = 1, int iterations = 3,
+                   double alpha = 0.9999, double loading = 1e-3, double floor = 1e-10) {
+        crlot_wpe_desc d{};
+        check(crlot_wpe_desc_default(&d), "crlot_wpe_desc_default");
+        d.mics = mics, d.taps = taps, d.delay = delay, d.iterations = iterations;
+        d.alpha = alpha, d.loading = loading, d.floor = floor;
+        check(crlot_wpe_create(plan, &d, groups, &w_), "crlot_wpe_create");
+    }
+    Dereverberator(crlot_plan* plan, const crlot_wpe_desc& d, int groups) {
+        check(crlot_wpe_create(plan, &d, groups, &w_), "crlot_wpe_create");
+    }
+    ~Dereverberator() { crlot_wpe_destroy(w_); }
+    Dereverberator(const Dereverberator&) = delete;
+    Dereverberator& operator=(const Dereverberator&) = delete;
+    Dereverberator(Dereverberator&& o) noexcept : w_(o.w_) { o.w_ = nullptr; }
+    Dereverberator& operator=(Dereverberator&& o) noexcept {
+        if (this != &o) {
+            crlot_wpe_destroy(w_);
+            w_ = o.w_;
+            o.w_ = nullptr;
+        }
+        return *this;
+    }
+    void prepare() { check(crlot_wpe_prepare(w_), "crlot_wpe_prepare"); }
+    void reset() { check(crlot_wpe_reset(w_), "crlot_wpe_reset"); }
+    int groups() const { return info(0); }
+    int mics() const { return info(1); }
+    int taps_count() const { return info(2); }
+    int delay() const { return info(3); }
+    int iterations() const { return info(4); }
+    int bins() const { return info(5); }
+    int64_t frames() const {
+        int64_t n = 0;
+        check(crlot_wpe_info(w_, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &n, nullptr, nullptr, nullptr),
+              "crlot_wpe_info");
+        return n;
+    }
+    // device blocks: the state [groups][L L + 2 L M][bins] floats, the inverse correlation
+    // matrix [groups][L L][bins] floats, the taps [groups][L][M][bins] float pairs
+    float* state() {
+        float* p = nullptr;
+        check(crlot_wpe_state(w_, &p), "crlot_wpe_state");
+        return p;
+    }
+    float* inv_cov() {
+        float* p = nullptr;
+        check(crlot_wpe_inv_cov(w_, &p), "crlot_wpe_inv_cov");
+        return p;
+    }
+    float* taps() {
+        float* p = nullptr;
+        check(crlot_wpe_taps(w_, &p), "crlot_wpe_taps");
+        return p;
+    }
+    crlot_wpe_launch last_launch() const {
+        crlot_wpe_launch r{};
+        check(crlot_wpe_last_launch(w_, &r), "crlot_wpe_last_launch");
+        return r;
+    }
+    void power_device(const float* d_z, int64_t ld_z, int64_t ldf_z, int n_groups, int64_t f0, int64_t f1, float* d_pow,
+                      int64_t ld_pow, int64_t ldf_pow, hipStream_t s = nullptr) {
+        check(crlot_wpe_power(w_, d_z, ld_z, ldf_z, n_groups, f0, f1, d_pow, ld_pow, ldf_pow, s), "crlot_wpe_power");
+    }
+    // carry: continue from and advance the state (d_state_out may be null), else fresh into d_state_out
+    void accumulate_device(const float* d_spec, int64_t ld_spec, int64_t ldf_spec, const float* d_pow, int64_t ld_pow,
+                           int64_t ldf_pow, int n_groups, int64_t f0, int64_t f1, bool carry, float* d_state_out,
+                           hipStream_t s = nullptr) {
+        check(crlot_wpe_accumulate(w_, d_spec, ld_spec, ldf_spec, d_pow, ld_pow, ldf_pow, n_groups, f0, f1, carry ? 1 : 0,
+                                   d_state_out, s),
+              "crlot_wpe_accumulate");
+    }
+    // null blocks: the object's
+    void solve_device(const float* d_state, int n_groups, float* d_taps, hipStream_t s = nullptr) {
+        check(crlot_wpe_solve(w_, d_state, n_groups, d_taps, s), "crlot_wpe_solve");
+    }
+    void filter_device(const float* d_spec, int64_t ld_spec, int64_t ldf_spec, const float* d_taps, int n_groups,
+                       int64_t f0, int64_t f1, float* d_out, int64_t ld_out, int64_t ldf_out, hipStream_t s = nullptr) {
+        check(crlot_wpe_filter(w_, d_spec, ld_spec, ldf_spec, d_taps, n_groups, f0, f1, d_out, ld_out, ldf_out, s),
+              "crlot_wpe_filter");
+    }
+    void rls_device(const float* d_spec, int64_t ld_spec, int64_t ldf_spec, int64_t f0, int64_t f1, float* d_out,
+                    int64_t ld_out, int64_t ldf_out, hipStream_t s = nullptr) {
+        check(crlot_wpe_rls(w_, d_spec, ld_spec, ldf_spec, f0, f1, d_out, ld_out, ldf_out, s), "crlot_wpe_rls");
+    }
+    // stft -> iterations x (power, accumulate, solve, filter) -> istft_ola, everything between in the plan's scratch
+    void dereverb_device(const float* d_x, int64_t ld_x, float* d_y, int64_t ld_y, int n_groups, int64_t T,
+                         hipStream_t s = nullptr) {
+        check(crlot_wpe(w_, d_x, ld_x, d_y, ld_y, n_groups, T, s), "crlot_wpe");
+    }
+    // one hop of the per-hop chain between the analysis half of st_in and the synthesis half of st_out;
+    // returns the samples per channel written to d_hop_out (0 or the hop size)
+    int hop_device(crlot_stream* st_in, crlot_stream* st_out, const float* d_hop_in, float* d_hop_out,
+                   hipStream_t s = nullptr) {
+        int32_t emitted = 0;
+        check(crlot_stream_wpe_hop(st_in, st_out, w_, d_hop_in, d_hop_out, &emitted, s), "crlot_stream_wpe_hop");
+        return emitted;
+    }
+    crlot_dereverberator* get() const { return w_; }
+
+   private:
+    int info(int which) const {
+        int32_t v[6] = {0, 0, 0, 0, 0, 0};
+        check(crlot_wpe_info(w_, &v[0], &v[1], &v[2], &v[3], &v[4], &v[5], nullptr, nullptr, nullptr, nullptr),
+              "crlot_wpe_info");
+        return v[which];
+    }
+    crlot_dereverberator* w_ = nullptr;
+};
+
 // Real-time per-hop streaming with hops in host memory (BASELINE config 4):
 // the resident kernel behind crlot_stream_rt_*.  push_hop copies one hop of
 // channels x H samples in ([H][C] interleaved PCM or [C][H]), returns the H
